@@ -9,8 +9,12 @@ correction, normalisation, and the D2H copy of every grid.  All per-parameter / 
 step; the sample columns are already in HBM (upload time reported separately, never in `value`).
 
     python bench.py --gpus N --steps K --warmup W       (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --dump-outputs DIR              (also write what the last timed step returned, as DIR/<name>.npy)
+    python bench.py ... --full                          (also every measurement below)
 
-After the timed region rank 0 adds, on one GPU only (SURVEY.md 8d protocol):
+A plain run sets up, warms up, times the K steps, writes its outputs if asked to and prints the result line; `ms_per_step` is
+the time of one timed step.  With --full the same K steps are then run again as a stream of triangles (`value_pipelined`),
+and rank 0 adds, on one GPU only (SURVEY.md 8d protocol):
   * roofline: the batched 2D binning kernel timed with HIP events on the library's stream, priced by its HBM counter
     traffic (profiles/r02_pmc_hist2d.json, separate rocprofv3 --pmc passes) and by the unit-weight streaming model;
   * cpu_baseline: the oracle (numpy/scipy restatement of the reference) on the GPU box's host cores -- all 50
@@ -52,11 +56,15 @@ LDS_ROOF_FILE = os.path.join(ROOT, "profiles", "r03_lds_atomic_roof.json")
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="number of timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the pipelined stream of "
+                    "triangles, the binning roofline and (unless --no-cpu-baseline) the CPU baseline with its parity checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned to DIR/<name>.npy "
+                    "(float64; every grid read at a fixed, seeded sample of points)")
     ap.add_argument("--nsamples", type=int, default=10_000_000)
     ap.add_argument("--nparams", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and parity")
     ap.add_argument("--profile", action="store_true", help="cProfile the timed steps (host side) to stderr")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo for "
                     "exercising the multi-rank path on a single GPU)")
@@ -71,7 +79,10 @@ def parse():
                     "census (hosts with >= 64 cores); abandoned and reported as such beyond it")
     ap.add_argument("--context-factory", default="", help="testing only: 'module:attr' of a Context stand-in (the CPU "
                     "suite runs the launcher and the multi-rank step with tests/fake_ctx.py); the product path never sets it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks_if_needed(args):
@@ -809,6 +820,37 @@ def cpu_baseline_and_parity(args, mc, s, names, ranges, pairs_all, dens):
     return cpu, parity_block
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much (the grids of a triangle are 642 MB)
+
+
+def dump_outputs(path, mc, pairs, dens):
+    """
+    --dump-outputs: what the timed path handed its caller in its last step, one float64 array per file, so that two builds
+    can be compared output for output.  ``pairs`` (npairs, 2) in the order of ``dens``; per density the grid shape, the
+    axis ends, the sum of P, the bandwidth triple (hx, hy, c) and its branch (A/B/C = 0/1/2, NaN when none), the contour
+    levels when the path made them, and P read at the same seeded fractional positions on every grid (P_sample); the
+    step's base statistics (means, fullcov).
+    """
+    os.makedirs(path, exist_ok=True)
+    pairs = np.asarray(pairs, dtype=np.float64).reshape(-1, 2)
+    npts = int(max(16, min(4096, DUMP_BYTES // (8 * max(len(dens), 1)))))
+    u = np.random.default_rng(np.random.SeedSequence([20261016, 1])).random((npts, 2))
+    sample = np.empty((len(dens), npts))
+    for k, d in enumerate(dens):
+        ny, nx = d.P.shape
+        sample[k] = d.P[(u[:, 0] * ny).astype(np.int64), (u[:, 1] * nx).astype(np.int64)]
+    nan3 = (np.nan, np.nan, np.nan)
+    out = dict(pairs=pairs, grid_shape=[d.P.shape for d in dens], axes=[(d.x[0], d.x[-1], d.y[0], d.y[-1]) for d in dens],
+               P_sum=[float(np.sum(d.P)) for d in dens], P_sample=sample,
+               bandwidth=[nan3 if d.bandwidth is None else d.bandwidth for d in dens],
+               bandwidth_branch=[np.nan if d.bandwidth_branch is None else "ABC".index(d.bandwidth_branch) for d in dens],
+               means=mc.means, fullcov=mc.fullcov)
+    if dens and all(d.contours is not None for d in dens):
+        out["contours"] = [np.asarray(d.contours, dtype=np.float64) for d in dens]
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
     spawn_ranks_if_needed(args)
@@ -916,10 +958,12 @@ def main():
         step_returned.append(time.perf_counter())
     barrier()
     elapsed = time.perf_counter() - t0
-    # ---- the same K steps as a stream of triangles: the PCIe copy of step k's grids (642 MB) lands while step k + 1 computes
-    # (what a caller that keeps asking for triangles gets: reported beside the headline, never as `value`)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mc, _REPLAY["last_pairs"], dens)
+    # ---- (--full) the same K steps as a stream of triangles: the PCIe copy of step k's grids (642 MB) lands while step k + 1
+    # computes (what a caller that keeps asking for triangles gets: reported beside the headline, never as `value`)
     pipelined_ms = None
-    if prof is None:
+    if args.full and prof is None:
         ts = time.perf_counter()
         for _ in range(args.steps):
             dens = one_step(mc, pairs_all, dist, rank, world, torch_device, args.emulate_world, comm)
@@ -965,8 +1009,8 @@ def main():
                        "parallelism": "pairs partitioned over %d GPU(s), samples replicated" % world,
                        "timed_region": "K triangles one after the other, each with all its grids on the host before the next "
                                        "starts (SURVEY 8d's t); value = pairs / that time.  value_pipelined / "
-                                       "ms_per_step_pipelined = the same K steps with the PCIe copy of a step's grids (642 MB) "
-                                       "landing while the next step computes",
+                                       "ms_per_step_pipelined (--full) = the same K steps with the PCIe copy of a step's grids "
+                                       "(642 MB) landing while the next step computes",
                        "setup_s": {"generate": round(t_gen, 2), "construct_upload_basestats": round(t_ctor, 2)}},
         }
         if dist is not None:
@@ -981,7 +1025,7 @@ def main():
         if args.emulate_world:
             line["emulated_world"] = args.emulate_world
             line["n_gpus"] = args.emulate_world
-        if world == 1 and not args.emulate_world:
+        if args.full and world == 1 and not args.emulate_world:
             line["roofline"] = binning_kernel_roofline(mc, pairs_all)
             if not args.no_cpu_baseline:
                 order = {tuple(pr): k for k, pr in enumerate(np.asarray(_REPLAY["last_pairs"]).tolist())}

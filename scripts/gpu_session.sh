@@ -3,7 +3,7 @@
 # Stages write under gpurun_out/<tag>/ (merged back by gpurun); the summaries that are judged are copied to profiles/ by hand.
 #   tests        pytest -m gpu (whole suite)            tests:<expr>  pytest -m gpu -k <expr>
 #   conv         scripts/conv_bench.py under rocprofv3 --kernel-trace --stats (one 136-pair batch of the convolution stage)
-#   bench        bench.py --steps 40 --warmup 5 --no-cpu-baseline      benchfull   bench.py (the driver's invocation)
+#   bench        bench.py --steps 40 --warmup 5 --full --no-cpu-baseline   benchfull   bench.py --full
 #   trace        rocprofv3 kernel trace + stream timeline of 4 bench steps
 #   c2 / c4 / c5 scripts/run_configs.py <config> (+ kernel trace for c4)
 #   kernels      scripts/kernels_isolated.py (isolated O(N) kernels)
@@ -33,12 +33,12 @@ for r in csv.DictReader(open(sys.argv[1])):
     if float(r["Percentage"]) > 0.4: print("%-60s calls %4s avg %9.1f us" % (r["Name"][:60], r["Calls"], float(r["AverageNs"]) / 1e3))
 PY
             ;;
-        bench) GETDIST_AMD_LIVE_PMC=0 timeout 400 python bench.py --steps 40 --warmup 5 --no-cpu-baseline > "$O/bench_40.json" 2> "$O/bench_40.err"
+        bench) GETDIST_AMD_LIVE_PMC=0 timeout 400 python bench.py --steps 40 --warmup 5 --full --no-cpu-baseline > "$O/bench_40.json" 2> "$O/bench_40.err"
                python -c "import json,sys; d=json.loads(open('$O/bench_40.json').read().strip().splitlines()[-1]); print('delivered triangle ms', d['ms_per_step'], 'value', d['value'], 'pipelined ms', d['ms_per_step_pipelined'], 'roofline', d['roofline']['frac'], d['roofline']['ms_per_launch'])" ;;
-        benchfull) timeout 900 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"
+        benchfull) timeout 900 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"
                python -c "import json,sys; d=json.loads(open('$O/bench_default.json').read().strip().splitlines()[-1]); print('ms_per_step', d['ms_per_step'], 'value', d['value'], 'roofline', d['roofline']['frac'], 'cpu', d['cpu_baseline']['value'], 'parity loose', d.get('parity',{}).get('n_pairs_on_loose_gate'))" ;;
         trace)
-            prof bench python "$GRAFT_REPO_ROOT/bench.py" --steps 4 --warmup 2 --no-cpu-baseline
+            prof bench python "$PWD/bench.py" --steps 4 --warmup 2 --full --no-cpu-baseline
             python scripts/stream_timeline.py "$(find "$O/prof_bench" -name '*kernel_trace.csv' | head -1)" 4 0.1 > "$O/bench_stream_timeline.txt" 2>&1
             rm -rf "$O/prof_bench"; head -30 "$O/bench_kernel_stats.csv" | cut -c1-150 ;;
         c2|c5) timeout 900 python scripts/run_configs.py "$stage" > "$O/config_$stage.json" 2> "$O/config_$stage.err"; tail -c 600 "$O/config_$stage.json" ;;
@@ -50,7 +50,7 @@ PY
         pmcc4) timeout 900 python scripts/pmc_kernels.py "$O/pmc_c4.json" --match k_cov,k_col_pass -- python "$GRAFT_REPO_ROOT/scripts/run_configs.py" c4 2>&1 | tail -6 ;;
         emulate)
             for W in 2 4 8; do
-                GETDIST_AMD_LIVE_PMC=0 timeout 300 python bench.py --steps 30 --warmup 5 --emulate-world $W --no-cpu-baseline > "$O/emulate_w$W.json" 2> "$O/emulate_w$W.err"
+                GETDIST_AMD_LIVE_PMC=0 timeout 300 python bench.py --steps 30 --warmup 5 --full --emulate-world $W --no-cpu-baseline > "$O/emulate_w$W.json" 2> "$O/emulate_w$W.err"
                 python -c "import json; d=json.loads(open('$O/emulate_w$W.json').read().strip().splitlines()[-1]); print('W', $W, 'ms_per_step', d['ms_per_step'])"
             done ;;
         emu_c3) GETDIST_AMD_LIVE_PMC=0 timeout 600 python scripts/emulate_scaling.py --nparams 50 --nsamples 10000000 > "$O/emulate_c3.json" 2> "$O/emulate_c3.err"; cat "$O/emulate_c3.err" | grep "^W=" ;;
@@ -77,7 +77,7 @@ PY
               for rep in 1 2 3; do
                   for side in base "$SW"; do
                       if [ "$side" = base ]; then envs="GDAMD_AB=base"; else envs="$SW"; fi
-                      env $envs GETDIST_AMD_LIVE_PMC=0 timeout 400 python bench.py --steps 30 --warmup 5 --no-cpu-baseline > "$O/ab_tmp.json" 2> "$O/ab_tmp.err"
+                      env $envs GETDIST_AMD_LIVE_PMC=0 timeout 400 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline > "$O/ab_tmp.json" 2> "$O/ab_tmp.err"
                       python -c "import json; d=json.loads(open('$O/ab_tmp.json').read().strip().splitlines()[-1]); print('$side', 'delivered', round(d['ms_per_step'],3), 'pipelined', round(d['ms_per_step_pipelined'],3))" | tee -a "$O/ab_${SW%%=*}.txt"
                   done
               done ;;

@@ -52,6 +52,21 @@ def meanlikes_cases(zoo, g):
                    {k: v for k, v in kw.items() if k != "fine_bins"}, fx, ll)
 
 
+def reference_bandwidths(gold, names, pairs, kw, fallback):
+    """
+    The (hx, hy, c) triples the reference itself used for ``pairs`` under the settings ``kw`` (stored beside its grids in
+    the fixture's golden file as <key>/hxhyc), and ``fallback`` (the oracle's triples) where the file has none.  Injected
+    into the device, they make the "same bandwidths in -> same grids out" checks independent of the host CPU: on pairs where
+    the reference's TNC is chaotic (tests/golden/tnc_chaotic_pairs.json) the oracle run with another numpy / BLAS build or
+    instruction set lands on another admissible triple, and the reference's grid is not the grid of that triple.
+    """
+    out = []
+    for (a, b), bw in zip(pairs, fallback):
+        key = "p2d/%s/%s/%s/hxhyc" % (names[a], names[b], kwkey(kw))
+        out.append(tuple(float(v) for v in gold[key]) if key in gold.files else bw)
+    return out
+
+
 def likes_outliers(a, ref, tol=1e-6):
     """
     Number of pixels where two mean-likelihood grids differ by more than tol.  The reference's FFT route leaves a

@@ -241,8 +241,9 @@ def test_density_2d(zoo, name):
         # no more loose pairs than pairs on which the oracle itself is chaotic
         assert len(report["loose"]) <= report["tnc_pairs_chaotic_in_the_oracle"], (name, report)
         if oracle_bw[0][0] is not None:
-            # same bandwidths in -> same grids out, for every pair, at the strict tolerance
-            dens = mc.get2DDensities(fx["pairs"], _bandwidths=oracle_bw, **kw)
+            # same bandwidths in -> same grids out, for every pair, at the strict tolerance (the reference's own triples)
+            ref_bw = gu.reference_bandwidths(g, fx["names"], fx["pairs"], kw, oracle_bw)
+            dens = mc.get2DDensities(fx["pairs"], _bandwidths=ref_bw, **kw)
             for (a, b), d in zip(fx["pairs"], dens):
                 key = "p2d/%s/%s/%s" % (fx["names"][a], fx["names"][b], gu.kwkey(kw))
                 gu.check_grid_2d(g, key, d.P, TOL_GRID)
@@ -437,8 +438,10 @@ def test_meanlikes_golden(zoo):
                 assert err < TOL_GRID, (case, a, b, err)
             bad = gu.likes_outliers(d.likes, o["likes"], TOL_GRID)
             assert bad <= gu.MAX_LIKES_OUTLIERS, (case, a, b, bad)
-        # identical bandwidths in -> the reference's likes grids out (up to its own noise-decided pixels)
-        dens = mc.get2DDensities(pairs, meanlikes=True, _bandwidths=oracle_bw, **kw2)
+        # identical bandwidths in (the reference's own triples) -> the reference's likes grids out (up to its own
+        # noise-decided pixels)
+        ref_bw = gu.reference_bandwidths(gu.load(case.split("/")[0]), fx["names"], pairs, kw2, oracle_bw)
+        dens = mc.get2DDensities(pairs, meanlikes=True, _bandwidths=ref_bw, **kw2)
         for (a, b), d in zip(pairs, dens):
             st = int(g["%s/2d/%d_%d/stride" % (case, a, b)])
             bad = gu.likes_outliers(d.likes[::st, ::st], g["%s/2d/%d_%d/likes" % (case, a, b)], TOL_GRID)

@@ -873,7 +873,7 @@ def test_bench_cpu_baseline_and_all_pairs_census_run_on_the_numpy_double(tmp_pat
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--nsamples", "20000", "--nparams", "8", "--steps", "1", "--warmup", "1",
-           "--cpu-small-n", "6000", "--cpu-workers", "2", "--context-factory", "fake_ctx:FakeContext"]
+           "--cpu-small-n", "6000", "--cpu-workers", "2", "--context-factory", "fake_ctx:FakeContext", "--full"]
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -883,6 +883,43 @@ def test_bench_cpu_baseline_and_all_pairs_census_run_on_the_numpy_double(tmp_pat
     full = par["full_size_census"]
     assert full["ran"] and full["pairs_compared"] == 28 and full["pairs_above_1e_6"] == 0 and full["N"] == 20000
     assert line["cpu_baseline"]["full_triangle_small_n"]["parity_census"]["pairs_compared"] == 28
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, adds none of the post-clock legs, and --dump-outputs
+    writes what the last timed step returned: float64 arrays, identical from run to run, grids equal to a direct call."""
+    import json
+    import subprocess
+
+    env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "tests"))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    runs = []
+    for k in range(2):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--nsamples", "20000", "--nparams", "8", "--steps", "3", "--warmup",
+               "1", "--context-factory", "fake_ctx:FakeContext", "--dump-outputs", str(tmp_path / ("out%d" % k))]
+        out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        runs.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    line = runs[0]
+    assert line["steps"] == 3 and len(line["ms_between_delivered_triangles"]) == 3 and line["ms_per_step"] > 0
+    assert line["unit"] == "densities/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert "roofline" not in line and "cpu_baseline" not in line and line["ms_per_step_pipelined"] is None
+    names = sorted(os.listdir(tmp_path / "out0"))
+    assert names == sorted(os.listdir(tmp_path / "out1")) and "P_sample.npy" in names and "pairs.npy" in names
+    assert sum(os.path.getsize(tmp_path / "out0" / f) for f in names) <= 64 << 20
+    for f in names:
+        a, b = np.load(tmp_path / "out0" / f), np.load(tmp_path / "out1" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), f
+    from getdist_amd import synth
+    from getdist_amd.mcsamples import MCSamples
+
+    s, w, names_, ranges = synth.config_c3(20000, 8)
+    mc = MCSamples(samples=s, weights=w, names=names_, ranges=ranges, _context_factory=FakeContext)
+    pairs = np.load(tmp_path / "out0" / "pairs.npy").astype(int)
+    dens = mc.get2DDensities([tuple(p) for p in pairs])
+    assert len(pairs) == 28
+    assert np.array_equal(np.load(tmp_path / "out0" / "P_sum.npy"), [np.sum(d.P) for d in dens])
 
 
 def test_comm_stage_timeout_never_undercuts_the_library_watchdog(monkeypatch):
