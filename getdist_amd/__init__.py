@@ -14,7 +14,7 @@ __version__ = "0.1.0"
 _EXPORTS = {
     "MCSamples": "mcsamples", "MCSamplesError": "mcsamples", "SettingError": "mcsamples", "BandwidthError": "mcsamples",
     "ParamError": "mcsamples", "WeightedSampleError": "mcsamples", "MargeStats": "mcsamples", "ParamLimit": "mcsamples",
-    "covToCorr": "mcsamples", "Density1D": "densities", "Density2D": "densities", "GridDensity": "densities",
+    "covToCorr": "mcsamples", "Density1D": "densities", "Density2D": "densities", "DensityND": "densities", "GridDensity": "densities",
     "DensitiesError": "densities", "getContourLevels": "densities", "nearestFFTnumber": "convolve",
     "loadMCSamples": "chainfiles", "chainFiles": "chainfiles", "prefill_plot_caches": "plotting",
 }

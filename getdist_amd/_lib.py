@@ -147,7 +147,11 @@ SIGNATURES = {
     "gd_comm_rccl_path": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     "gd_upload_shard": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
     "gd_comm_share_columns": (C.c_int, [_p, C.POINTER(C.c_int64)]),
+    "gd_histnd_batch": (C.c_int, [_p, _i32, _pi32, _pi32, _pd, _pd, _i32, _i32, _i32, _pd, _pd, _pd]),
 }
+
+GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
+GD_HISTND_H, GD_HISTND_LIKES, GD_HISTND_LMIN = 1, 2, 4
 
 _lib = None
 
@@ -659,6 +663,21 @@ class Context:
             int(winw), int(flags), int(bco), int(mbc), None if mb is None else _dp(mb), None if mm is None else _dp(mm),
             None if zm is None else zm.ctypes.data_as(C.POINTER(C.c_ubyte)), out.ptr, _ip(status)))
         return out, status
+
+    def histnd_batch(self, dims, cols, binmin, width, nb, want_h=True, want_likes=False, want_lmin=False, loglike_col=-1):
+        """Raw N-D histograms of B densities in one call (gd_histnd_batch): density b bins the dims[b] columns
+        cols[o_b:o_b + dims[b]] (axis 0 first; binmin / width laid out like cols) into nb bins per axis.  Returns
+        (H, HL, Lmin): flat host arrays holding the B grids back to back (density b: nb**dims[b] entries, axis 0 fastest),
+        None for an output not asked for.  HL needs the like weights of like_weights(..., mode=0)."""
+        dims, cols, binmin, width = _i32arr(dims), _i32arr(cols), _f64arr(binmin), _f64arr(width)
+        if cols.size != int(dims.sum()) or binmin.size != cols.size or width.size != cols.size:
+            raise ValueError("cols, binmin and width need one entry per axis of every density")
+        total = int(sum(int(nb) ** int(d) for d in dims))
+        flags = (GD_HISTND_H if want_h else 0) | (GD_HISTND_LIKES if want_likes else 0) | (GD_HISTND_LMIN if want_lmin else 0)
+        out = [np.empty(total) if f & flags else None for f in (GD_HISTND_H, GD_HISTND_LIKES, GD_HISTND_LMIN)]
+        self._check(self.lib.gd_histnd_batch(self.h, len(dims), _ip(dims), _ip(cols), _dp(binmin), _dp(width), int(nb),
+                                             flags, int(loglike_col), *[None if a is None else _dp(a) for a in out]))
+        return tuple(out)
 
     # ---- auxiliary vectors
     EXTRA_COLS = 4

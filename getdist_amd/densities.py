@@ -327,3 +327,62 @@ class Density2D(GridDensity):
     def Prob(self, x, y, grid=False):
         """Interpolated density at the points (x, y), or on their outer product with ``grid=True``."""
         return self(x, y, grid=grid)
+
+
+class DensityND(GridDensity):
+    """
+    N-D marginalised density on a regular grid (densities.py:304-381): ``xs`` lists the coordinate arrays in parameter
+    order, ``axes = xs[::-1]`` is the index order of ``P`` (the last parameter first), ``x`` / ``y`` / ``z`` are the
+    first three of ``xs`` and ``spacing`` is the cell volume.  ``integrate`` is the reference's, quirk included (see
+    there).  There is no interpolation: the reference's ``Prob`` hands its LinearNDInterpolator the axes as if they were
+    points, which fails for every grid, so ``Prob`` / ``__call__`` raise NotImplementedError.
+    """
+
+    def __init__(self, xs, P=None, view_ranges=None):
+        self.dim = len(xs)
+        self.x = xs[0]
+        if self.dim >= 2:
+            self.y = xs[1]
+        if self.dim >= 3:
+            self.z = xs[2]
+        self.xs = xs
+        self.axes = xs[::-1]
+        self.view_ranges = view_ranges
+        self.spacing = 1.0
+        for ax in xs:
+            self.spacing = self.spacing * (ax[1] - ax[0])
+        self.likes = self.maxlikes = self.contours = self.maxcontours = None
+        self.setP(P)
+
+    def integrate(self, P):
+        """The reference's DensityND.integrate (densities.py:344-372): the sum of P over the cells with k indices on the
+        first or last value of their axis, weighted 1/2^k -- NOT multiplied by ``spacing`` (getRawNDDensity(normalized=True)
+        divides by this).  Summed cell by cell in C order per k, as the reference's loop does; its table of classes has
+        len(P) + 1 entries (the size of the first axis, not the dimension), so a grid with more boundary classes than that
+        raises IndexError there and here."""
+        P = np.asarray(P)
+        multinorm = np.zeros(len(P) + 1)
+        nbnd = np.zeros(P.shape, dtype=np.int64)
+        for axis, size in enumerate(P.shape):
+            i = np.arange(size).reshape([-1 if a == axis else 1 for a in range(P.ndim)])
+            nbnd = nbnd + (i == 0) + (i == size - 1)
+        flat, cls = P.reshape(-1), nbnd.reshape(-1)
+        if cls.size and cls.max() >= multinorm.size:
+            raise IndexError("index %d is out of bounds for axis 0 with size %d" % (cls.max(), multinorm.size))
+        for k in range(multinorm.size):
+            sel = flat[cls == k]
+            if sel.size:
+                multinorm[k] += np.cumsum(sel)[-1]  # sequential, in C order (np.sum would add pairwise)
+        norm = 0.0
+        for i in range(len(multinorm)):
+            norm += multinorm[i] / 2**i
+        return norm
+
+    def _initSpline(self):
+        raise NotImplementedError("DensityND has no interpolation (the reference's LinearNDInterpolator call fails for "
+                                  "every grid: it is given the axes as points)")
+
+    def Prob(self, xs):
+        self._initSpline()
+
+    __call__ = Prob

@@ -29,7 +29,8 @@ DEFAULT_SETTINGS = dict(
     ignore_rows=0.0, min_weight_ratio=1e-30, contours=[0.68, 0.95, 0.99], credible_interval_threshold=0.05,
     range_ND_contour=-1, range_confidence=0.001, corr_length_thin=0, corr_length_steps=15, converge_test_limit=0.95, fine_bins=1024, smooth_scale_1D=-1.0,
     boundary_correction_order=1, mult_bias_correction_order=1, smooth_scale_2D=-1.0, max_corr_2D=0.99,
-    fine_bins_2D=256, use_effective_samples_2D=False, max_scatter_points=2000, num_bins=100, num_bins_2D=40)
+    fine_bins_2D=256, use_effective_samples_2D=False, max_scatter_points=2000, num_bins=100, num_bins_2D=40,
+    num_bins_ND=12)  # (num_bins_ND: the class default of mcsamples.py:224, read from an ini too, :407)
 
 
 class WeightedSampleError(Exception):
@@ -439,6 +440,22 @@ def _g2_independence_vs_markov(tran2, thin_rows):
                 return None
             g2 += np.log(float(focus) / fitted) * float(focus)
     return 2 * g2
+
+
+def _set_raw_edge_mask_nd(parv, prior_mask):
+    """mcsamples.py:2012-2033: halve the faces of the raw N-D grid on the bounded sides.  Axis i of the mask (C order,
+    the last parameter first) belongs to parv[::-1][i]."""
+    vrap = parv[::-1]
+    if prior_mask.ndim != len(parv):
+        raise ValueError("parv and prior_mask or different sizes!")
+    for i, par in enumerate(vrap):
+        sl = [slice(None)] * prior_mask.ndim
+        if par.has_limits_bot:
+            sl[i] = 0
+            prior_mask[tuple(sl)] /= 2
+        if par.has_limits_top:
+            sl[i] = prior_mask.shape[i] - 1
+            prior_mask[tuple(sl)] /= 2
 
 
 def _set_edge_mask_2d(parx, pary, prior_mask, winw):
@@ -2218,6 +2235,136 @@ class MCSamples:
                 self.density1D[par.name] = d
             out.append(d)
         return out
+
+    # ---- raw N-D densities (mcsamples.py:2012-2235) ---------------------------------------------------------------
+    def getRawNDDensity(self, xs, normalized=False, **kwargs):
+        """DensityND of the unsmoothed histogram of the parameters ``xs`` (mcsamples.py:2094-2108): maximum 1, or with
+        ``normalized`` divided by DensityND.integrate.  kwargs as getRawNDDensityGridData."""
+        if self.needs_update:
+            self.updateBaseStatistics()
+        density = self.getRawNDDensityGridData(xs, get_density=True, **kwargs)
+        if density is not None and normalized:
+            density.normalize(in_place=True)
+        return density
+
+    def getRawNDDensityGridData(self, js, writeDataToFile=False, num_plot_contours=None, get_density=False,
+                                meanlikes=False, maxlikes=False, **kwargs):
+        """
+        Unsmoothed N-D marginalised density of the parameters ``js`` (mcsamples.py:2111-2235): a DensityND with maximum 1,
+        ``contours`` (unless ``get_density``), ``likes`` (mean likelihoods, maximum 1) with ``meanlikes``, and ``maxlikes``
+        (profile likelihood exp(min L - L_bin)) with ``maxcontours`` with ``maxlikes``.  None when a parameter is unknown.
+        kwargs: ``num_bins_ND`` and ``boundary_correction_order``.  ``writeDataToFile`` is not supported (this package
+        writes no plot-data files, for 1D and 2D densities neither) and raises NotImplementedError.
+        """
+        if writeDataToFile:
+            raise NotImplementedError("writeDataToFile: this package writes no plot-data files")
+        if self.needs_update:
+            self.updateBaseStatistics()
+        return self.getRawNDDensities([js], num_plot_contours=num_plot_contours, get_density=get_density,
+                                      meanlikes=meanlikes, maxlikes=maxlikes, **kwargs)[0]
+
+    def getRawNDDensities(self, param_lists, num_plot_contours=None, get_density=False, meanlikes=False, maxlikes=False,
+                          **kwargs):
+        """
+        Batched getRawNDDensityGridData (additive API): one DensityND (or None where a parameter is unknown) per list of
+        parameters in ``param_lists``; the lists may differ in length.  Every histogram of a batch comes from ONE native
+        call (gd_histnd_batch): each parameter's index column is made once and shared by the densities that use it.
+        """
+        if self.needs_update:
+            self.updateBaseStatistics()
+        for k in kwargs:
+            if k not in ("num_bins_ND", "boundary_correction_order"):
+                raise SettingError("unknown N-D density argument %s" % k)
+        if (meanlikes or maxlikes) and self.loglikes is None:
+            raise MCSamplesError("mean / profile likelihoods need the loglikes column")
+        nb = int(kwargs.get("num_bins_ND", self.num_bins_ND))
+        bco = kwargs.get("boundary_correction_order", self.boundary_correction_order)
+        jlists = []
+        for js in param_lists:
+            jv = [self._parAndNumber(j)[0] for j in js]
+            jlists.append(None if None in jv else jv)
+        todo = [b for b, jv in enumerate(jlists) if jv is not None]
+        out = [None] * len(jlists)
+        if not todo:
+            return out
+        if nb < 2:
+            raise SettingError("num_bins_ND must be at least 2")
+        from ._lib import GD_HISTND_MAX_BINS, GD_HISTND_MAXD
+
+        for b in todo:
+            if len(jlists[b]) > GD_HISTND_MAXD or nb ** len(jlists[b]) > GD_HISTND_MAX_BINS:
+                raise SettingError("raw N-D grid of %d^%d bins is above the limit of %d" % (nb, len(jlists[b]),
+                                                                                          GD_HISTND_MAX_BINS))
+        self._init_params([j for b in todo for j in jlists[b]])
+        names = self.paramNames.names
+        edges = {j: self._bin_edges(names[j], nb) for b in todo for j in jlists[b]}
+        want_likes = meanlikes and not get_density
+        want_max = maxlikes and not get_density
+        if want_likes:
+            self._use_like_weights(0)
+        ll_col = self.ctx.set_extra_column(self.ctx.EXTRA_COLS - 1, self.loglikes) if want_max else -1
+        if want_max:
+            bestfit = np.max(-self.loglikes)
+        # batches of at most _ND_BATCH_BINS grid entries (one native call each)
+        batches, cur, bins = [], [], 0
+        for b in todo:
+            M = nb ** len(jlists[b])
+            if cur and bins + M > self._ND_BATCH_BINS:
+                batches.append(cur)
+                cur, bins = [], 0
+            cur.append(b)
+            bins += M
+        batches.append(cur)
+        for batch in batches:
+            dims = [len(jlists[b]) for b in batch]
+            cols = [j for b in batch for j in jlists[b]]
+            H, HL, Lmin = self.ctx.histnd_batch(dims, cols, [edges[j][1] for j in cols], [edges[j][0] for j in cols], nb,
+                                                want_h=True, want_likes=want_likes, want_lmin=want_max, loglike_col=ll_col)
+            at = 0
+            for b, d in zip(batch, dims):
+                M = nb ** d
+                grids = [None if g is None else g[at:at + M].reshape((nb,) * d) for g in (H, HL, Lmin)]
+                at += M
+                out[b] = self._finish_nd(jlists[b], nb, bco, grids, num_plot_contours, get_density,
+                                         bestfit if want_max else None)
+        return out
+
+    _ND_BATCH_BINS = 1 << 24  # grid entries per native call (8 bytes per entry and output on the device and the host)
+
+    def _finish_nd(self, jv, nb, bco, grids, num_plot_contours, get_density, bestfit):
+        """The host tail of getRawNDDensityGridData (mcsamples.py:2150-2197) for one density from its device grids."""
+        from .densities import DensityND, getContourLevels
+
+        binsND, likes, Lmin = grids
+        parv = [self.paramNames.names[j] for j in jv]
+        ndim = len(parv)
+        if any(p.has_limits for p in parv) and bco >= 0:
+            prior_mask = np.ones((nb,) * ndim)
+            _set_raw_edge_mask_nd(parv, prior_mask)
+            binsND /= prior_mask
+        xv = []
+        for p in parv:
+            _, binmin, binmax = self._bin_edges(p, nb)
+            xv.append(np.linspace(binmin, binmax, nb))
+        views = [(p.range_min, p.range_max) for p in parv]
+        density = DensityND(xv, binsND, view_ranges=views)
+        density.normalize("max", in_place=True)
+        if get_density:
+            return density
+        ncontours = len(self.contours)
+        if num_plot_contours:
+            ncontours = min(num_plot_contours, ncontours)
+        contours = self.contours[:ncontours]
+        density.contours = density.getContourLevels(contours)
+        if likes is not None:
+            likes /= np.max(likes)
+            density.likes = likes
+        if Lmin is not None:
+            # max over a bin of exp(-bestfit - L) (the reference's loop, :2165-2171) = exp(-bestfit - min L): the
+            # subtraction and exp are monotone; an empty bin (+inf) gives 0, the loop's starting value
+            density.maxlikes = np.exp(-bestfit - Lmin)
+            density.maxcontours = getContourLevels(density.maxlikes, contours, half_edge=False)
+        return density
 
     # ---- marginalised limits (mcsamples.py:2353-2367, 2442-2531) -----------------------------------------------
     def _max_frac_twotail(self):

@@ -411,6 +411,35 @@ int gd_density2d_masked(gd_ctx* ctx, int32_t F, const void* d_hist, double rx, d
                         int32_t flags, int32_t bco, int32_t mbc, const double* mask_bc, const double* mask_mbc,
                         const unsigned char* zero_mask, void* d_P_out, int32_t* status_out);
 
+/* ---------------------------------------------------------------- raw N-D histograms -----------
+ * gd_histnd_batch: the binning of getRawNDDensityGridData (mcsamples.py:2121-2171) for B densities in one call.
+ *   Density b has dims[b] parameters: columns cols[o_b .. o_b + dims[b] - 1] (o_b = dims[0] + ... + dims[b-1], axis 0
+ *   first) with per-axis bin origins binmin[] and widths width[] laid out like cols.  Every axis has nb bins; the
+ *   index of sample i on an axis is (int)((x_i - binmin)/width + 0.5), bit-exact with the reference (the index
+ *   columns of gd_prebin8_batch for nb <= 256, of gd_prebin_batch above; each distinct (column, binmin, width) is
+ *   binned once per call), and the flat bin is q = ix_0 + nb ix_1 + nb^2 ix_2 + ... (_flattenValues).  Density b has
+ *   M_b = nb^dims[b] <= GD_HISTND_MAX_BINS bins; its grids start at element M_0 + ... + M_{b-1} of each output (host
+ *   fp64), so a grid read as a C array of shape (nb,)*d is indexed [ix_{d-1}, ..., ix_0].  flags select the outputs:
+ *     GD_HISTND_H      H_out[q]    = sum of the currently selected weights (unit when none) over the samples in q;
+ *     GD_HISTND_LIKES  HL_out[q]   = sum of the like-weight vector of gd_like_weights (build it in mode 0:
+ *                                    w exp(mean_loglike - L), mcsamples.py:2158);
+ *     GD_HISTND_LMIN   Lmin_out[q] = min of column loglike_col over the samples in q, +inf for an empty bin.
+ *   Deterministic: unit weights and integral multiplicities add integer counts (exactly np.bincount); real weights add
+ *   round(w 2^k) in 64-bit fixed point (2^k N max(w) < 2^61), so reruns are bit-equal; the min is an integer min of
+ *   an order-preserving encoding.  Tiers: a density whose counters (4 bytes per bin for counts, 8 for fixed point and
+ *   for each of HL / Lmin) fit 128 KB is binned in LDS per (density, chunk of rows) and flushed with integer atomics;
+ *   larger grids take global integer atomics.  Returns GD_ERR_BADARG for a grid above GD_HISTND_MAX_BINS, a dimension
+ *   outside 1..GD_HISTND_MAXD, missing like weights, or any sample whose index falls outside [0, nb) (checked before
+ *   it is counted: nothing is written out of bounds).  Blocks until the grids are in the host arrays. */
+#define GD_HISTND_MAXD 25
+#define GD_HISTND_MAX_BINS (1 << 25)
+#define GD_HISTND_H 1
+#define GD_HISTND_LIKES 2
+#define GD_HISTND_LMIN 4
+int gd_histnd_batch(gd_ctx* ctx, int32_t B, const int32_t* dims, const int32_t* cols, const double* binmin,
+                    const double* width, int32_t nb, int32_t flags, int32_t loglike_col, double* H_out, double* HL_out,
+                    double* Lmin_out);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
