@@ -148,10 +148,13 @@ SIGNATURES = {
     "gd_upload_shard": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
     "gd_comm_share_columns": (C.c_int, [_p, C.POINTER(C.c_int64)]),
     "gd_histnd_batch": (C.c_int, [_p, _i32, _pi32, _pi32, _pd, _pd, _i32, _i32, _i32, _pd, _pd, _pd]),
+    "gd_pca_corr": (C.c_int, [_p, _pi32, _i32, _pi32, _pd, _pd, _pd]),
+    "gd_pca_project": (C.c_int, [_p, _pi32, _i32, _pi32, _pd, _pd, _pd, _i32, _i32, _pd, _pd, _pd, _pd, _pd, _pd]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
 GD_HISTND_H, GD_HISTND_LIKES, GD_HISTND_LMIN = 1, 2, 4
+GD_PCA_MAX_PROJ = 448
 
 _lib = None
 
@@ -678,6 +681,34 @@ class Context:
         self._check(self.lib.gd_histnd_batch(self.h, len(dims), _ip(dims), _ip(cols), _dp(binmin), _dp(width), int(nb),
                                              flags, int(loglike_col), *[None if a is None else _dp(a) for a in out]))
         return tuple(out)
+
+    def pca_corr(self, cols, maps):
+        """Steps 1-2 of MCSamples.PCA (gd_pca_corr) over resident columns ``cols`` with per-column maps (0 N, 1 L, 2 M),
+        sample weights.  Returns (mean, sd, corr): the weighted means of the mapped columns, their standard deviations,
+        and the n x n weighted correlation matrix of the standardised columns (diagonal 1)."""
+        cols, maps = _i32arr(cols), _i32arr(maps)
+        if maps.size != cols.size:
+            raise ValueError("one map per column")
+        n = cols.size
+        mean, sd, corr = np.empty(n), np.empty(n), np.empty((n, n))
+        self._check(self.lib.gd_pca_corr(self.h, _ip(cols), n, _ip(maps), _dp(mean), _dp(sd), _dp(corr)))
+        return mean, sd, corr
+
+    def pca_project(self, cols, maps, mean, sd, U, doexp, all_means, all_sd):
+        """Steps 4-5 of MCSamples.PCA (gd_pca_project): per row p = U z (z: the standardised mapped columns), exp(p) when
+        ``doexp``.  Returns (newmean, newsd, pcpc, pcpar): weighted mean and standard deviation of each component, the
+        np x np correlations of the standardised components and their np x n_all correlations with the first n_all
+        resident columns standardised by ``all_means`` / ``all_sd``."""
+        cols, maps, mean, sd = _i32arr(cols), _i32arr(maps), _f64arr(mean), _f64arr(sd)
+        U, all_means, all_sd = _f64arr(U), _f64arr(all_means), _f64arr(all_sd)
+        n, n_all = cols.size, all_means.size
+        if maps.size != n or mean.size != n or sd.size != n or U.shape != (n, n) or all_sd.size != n_all:
+            raise ValueError("pca_project: inconsistent shapes")
+        newmean, newsd, pcpc, pcpar = np.empty(n), np.empty(n), np.empty((n, n)), np.empty((n, n_all))
+        self._check(self.lib.gd_pca_project(self.h, _ip(cols), n, _ip(maps), _dp(mean), _dp(sd), _dp(U), int(bool(doexp)),
+                                            n_all, _dp(all_means), _dp(all_sd), _dp(newmean), _dp(newsd), _dp(pcpc),
+                                            _dp(pcpar)))
+        return newmean, newsd, pcpc, pcpar
 
     # ---- auxiliary vectors
     EXTRA_COLS = 4

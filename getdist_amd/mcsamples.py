@@ -502,6 +502,7 @@ class MCSamples:
         self._loglikes_col = None
         self.label, self.name_tag = label, name_tag
         self.root = root
+        self.rootdirname = ""  # mcsamples.py:244: the output root of writeDataToFile (PCA writes rootdirname + ".PCA")
         self.raise_on_bandwidth_errors = False
         self.no_warning_params = []          # mcsamples.py:259-260,438-439: parameters whose 1D bandwidth fallback is silent
         self.no_warning_chi2_params = True
@@ -904,6 +905,17 @@ class MCSamples:
         self.paramNames.names.append(par)
         self._replace_samples(new, self.weights, self.loglikes, self.chain_offsets)
         return par
+
+    def parName(self, i, starDerived=False):
+        """mcsamples.py:348-356: the name of parameter ``i``, with a trailing * for a derived one when ``starDerived``"""
+        par = self.paramNames.names[i]
+        return par.name + "*" if starDerived and par.isDerived else par.name
+
+    def parLabel(self, i):
+        """mcsamples.py:358-368: the label of parameter ``i`` (an index or a name)"""
+        if isinstance(i, str):
+            return self.paramNames.parWithName(i).label
+        return self.paramNames.names[i].label
 
     # ---- what GetDist's plotting layer asks a sample set for besides densities (plots.py:655-690,933-955,2262-2290) ------
     def getParamNames(self):
@@ -2365,6 +2377,118 @@ class MCSamples:
             density.maxlikes = np.exp(-bestfit - Lmin)
             density.maxcontours = getContourLevels(density.maxlikes, contours, half_edge=False)
         return density
+
+    # ---- principal components (mcsamples.py:682-885) -----------------------------------------------------------
+    def PCA(self, params, param_map=None, normparam=None, writeDataToFile=False, filename=None, conditional_params=(),
+            n_best_only=None):
+        """
+        Principal component analysis of the parameters ``params`` (names not in the sample set are dropped), optionally
+        mapped (``param_map``: one of N, L (log), M (log of the negation) per parameter; by default L unless a parameter's
+        maximum is negative or its minimum is below a tenth of its range) and conditional on fixed values of
+        ``conditional_params``.  ``normparam`` gives that parameter unit power in every component (default: the largest).
+        Returns the text of mcsamples.py:682-885, or with ``n_best_only`` the tightest component's summary (1) or a list of
+        the ``n_best_only`` tightest; ``writeDataToFile`` writes the text to ``filename`` or ``rootdirname + ".PCA"``.
+        The O(N) passes run on the device (gd_pca_corr: means, standard deviations and the correlation matrix of the
+        mapped columns; gd_pca_project: the projected components' means, standard deviations and correlations); the
+        eigen-decomposition and the text stay on the host.
+        """
+        if self.needs_update:
+            self.updateBaseStatistics()
+        if getattr(self, "_column_share", None) is not None:
+            raise NotImplementedError("PCA needs every column resident on one device: this context holds only its rank's "
+                                      "share of the columns (multi-GPU PCA is not supported)")
+        logging.info("Doing PCA for %s parameters", len(params))
+        if len(conditional_params):
+            logging.info("conditional %u fixed parameters", len(conditional_params))
+        text = "PCA for parameters:\n"
+        params = [name for name in params if self.paramNames.parWithName(name)]
+        nparams = len(params)
+        indices = [self.index[p] for p in params] + [self.index[p] for p in conditional_params]
+        normparam = params.index(normparam) if normparam and normparam in params else -1
+        n = len(indices)
+        if param_map is None:
+            # param_min / param_max of _initParamRanges are the base statistics' column extrema
+            param_map = ""
+            for j in indices[:nparams]:
+                mn, mx = self._col_min[j], self._col_max[j]
+                param_map += "N" if mx < 0 or mn < (mx - mn) / 10 else "L"
+        maps = np.zeros(n, dtype=np.int32)
+        labels = []
+        for i in range(nparams):
+            label = self.parLabel(indices[i])
+            if param_map[i] == "L":
+                maps[i] = 1
+                labels.append("ln(" + label + ")")
+            elif param_map[i] == "M":
+                maps[i] = 2
+                labels.append("ln(-" + label + ")")
+            else:
+                labels.append(label)
+            text += "%10s :%s\n" % (str(indices[i] + 1), str(labels[i]))
+        doexp = bool(np.any(maps[:nparams] != 0))
+        PCmean, sd, corr = self.ctx.pca_corr(indices, maps)
+
+        text += "\nCorrelation matrix for reduced parameters\n"
+        for i in range(nparams):
+            text += "%12s :" % params[i] + "".join("%8.4f" % corr[j][i] for j in range(n)) + "\n"
+        if len(conditional_params):
+            u = np.linalg.inv(corr)
+            u = np.linalg.inv(u[np.ix_(range(nparams), range(nparams))])
+            n = nparams
+        else:
+            u = corr
+        evals, evects = np.linalg.eig(u)
+        isorted = evals.argsort()
+        u = np.transpose(evects[:, isorted])
+
+        text += "\ne-values of correlation matrix\n"
+        for i in range(n):
+            text += "PC%2i: %8.4f\n" % (i + 1, evals[isorted[i]])
+        text += "\ne-vectors\n"
+        for j in range(n):
+            text += "%3i:" % (indices[j] + 1) + "".join("%8.4f" % evects[j][isorted[i]] for i in range(n)) + "\n"
+        for i in range(n):
+            k = normparam if normparam != -1 else np.abs(u[i, :]).argmax()
+            u[i, :] = u[i, :] / u[i, k] * sd[k]
+
+        newmean, newsd, pcpc, pcpar = self.ctx.pca_project(indices[:n], maps[:n], PCmean[:n], sd[:n], u, doexp,
+                                                           self.means, self.sddev)
+        text += "\nPrincipal components\n"
+        mode_texts = []
+        for i in range(n):
+            summary = "PC%i (e-value: %f)\n" % (i + 1, evals[isorted[i]])
+            for j in range(n):
+                label = self.parLabel(indices[j])
+                if param_map[j] in ["L", "M"]:
+                    expo = "%f" % (1.0 / sd[j] * u[i][j])
+                    div = "%f" % (-np.exp(PCmean[j]) if param_map[j] == "M" else np.exp(PCmean[j]))
+                    summary += "[%f]  (%s/%s)^{%s}\n" % (u[i][j], label, div, expo)
+                else:
+                    expo = "%f" % (sd[j] / u[i][j])
+                    if doexp:
+                        summary += "[%f]   exp((%s-%f)/%s)\n" % (u[i][j], label, PCmean[j], expo)
+                    else:
+                        summary += "[%f]   (%s-%f)/%s\n" % (u[i][j], label, PCmean[j], expo)
+            summary += "          = %f +- %f\n\n" % (newmean[i], newsd[i])
+            mode_texts.append(summary)
+            text += summary
+
+        text += "Correlations of principal components\n"
+        text += "".join("%8i" % i for i in range(1, n + 1)) + "\n"
+        for j in range(n):
+            text += "PC%2i" % (j + 1) + "".join("%8.3f" % pcpc[i][j] for i in range(n)) + "\n"
+        for j in range(self.n):
+            text += "%4i" % (j + 1) + "".join("%8.3f" % pcpar[i][j] for i in range(n))
+            text += "   (%s)\n" % self.parLabel(j)
+
+        if writeDataToFile:
+            with open(filename or self.rootdirname + ".PCA", "w", encoding="utf-8") as f:
+                f.write(text)
+        if n_best_only:
+            if n_best_only == 1:
+                return mode_texts[0]
+            return mode_texts[:n_best_only]
+        return text
 
     # ---- marginalised limits (mcsamples.py:2353-2367, 2442-2531) -----------------------------------------------
     def _max_frac_twotail(self):

@@ -440,6 +440,32 @@ int gd_histnd_batch(gd_ctx* ctx, int32_t B, const int32_t* dims, const int32_t* 
                     const double* width, int32_t nb, int32_t flags, int32_t loglike_col, double* H_out, double* HL_out,
                     double* Lmin_out);
 
+/* ---------------------------------------------------------------- principal components --------
+ * The O(N) passes of MCSamples.PCA (mcsamples.py:682-885) over resident columns.  Per column a map is applied in registers:
+ * maps[c] = 0 (N: x), 1 (L: log x), 2 (M: log -x); a non-positive argument of a log gives -inf / NaN, which propagates.
+ * Both entries use the SAMPLE weights (unit when there are none), also while gd_select_weights(ctx, 1) has auxiliary
+ * weights selected, and norm = sum of those weights.  Two passes each, every sum taken as fixed-order block partials of
+ * v_mfma_f64_16x16x4_f64 tile products added in a fixed order (no floating-point atomics): reruns are bit-identical.
+ * No N x n scratch: maps, projection and exp are recomputed from the resident columns in each pass.  Returns
+ * GD_ERR_BADARG, before any launch, when no samples are uploaded, n (np) is outside 1..uploaded columns, a column index
+ * or map is out of range, or (gd_pca_project) np > GD_PCA_MAX_PROJ or n_all is outside 1..uploaded columns.  Both block
+ * until the results are in the host arrays.
+ *
+ * gd_pca_corr: steps 1-2.  y_c = map_c(x_{cols[c]}), c < n.  mean_out[c] = sum w y_c / norm (pass 1);
+ *   sd_out[c] = sqrt(sum w (y_c - mean_c)^2 / norm) and corr_out[i n + j] = sum w d_i d_j / norm / (sd'_i sd'_j) with
+ *   d = y - mean and sd' = sd where sd != 0, else 1 (pass 2).  The diagonal of corr_out is 1 by construction.
+ * gd_pca_project: steps 4-5 for the np analysed columns.  Per row z_k = (map_k(x_{cols[k]}) - mean[k]) / sd'_k,
+ *   p_i = sum_k U[i np + k] z_k, then exp(p_i) when doexp.  newmean_out[i] = sum w p_i / norm (pass 1);
+ *   newsd_out[i] = sqrt(sum w (p_i - newmean_i)^2 / norm), and with q_i = (p_i - newmean_i) / newsd_i
+ *   pcpc_out[i np + j] = sum w q_i q_j / norm and pcpar_out[i n_all + j] = sum w q_i (x_j - all_means[j]) / all_sd[j] / norm
+ *   over resident columns j < n_all (pass 2). */
+#define GD_PCA_MAX_PROJ 448
+int gd_pca_corr(gd_ctx* ctx, const int32_t* cols, int32_t n, const int32_t* maps, double* mean_out, double* sd_out,
+                double* corr_out);
+int gd_pca_project(gd_ctx* ctx, const int32_t* cols, int32_t np, const int32_t* maps, const double* mean, const double* sd,
+                   const double* U, int32_t doexp, int32_t n_all, const double* all_means, const double* all_sd,
+                   double* newmean_out, double* newsd_out, double* pcpc_out, double* pcpar_out);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
