@@ -12,9 +12,9 @@ there is no CPU fallback.
 __version__ = "0.1.0"
 
 _EXPORTS = {
-    "MCSamples": "mcsamples", "MCSamplesError": "mcsamples", "SettingError": "mcsamples", "BandwidthError": "mcsamples",
-    "ParamError": "mcsamples", "WeightedSampleError": "mcsamples", "MargeStats": "mcsamples", "ParamLimit": "mcsamples",
-    "covToCorr": "mcsamples", "Density1D": "densities", "Density2D": "densities", "DensityND": "densities", "GridDensity": "densities",
+    "MCSamples": "mcsamples", "MCSamplesError": "chains", "SettingError": "mcsamples", "BandwidthError": "mcsamples",
+    "ParamError": "chains", "WeightedSampleError": "chains", "MargeStats": "types", "ParamLimit": "types",
+    "covToCorr": "chains", "Density1D": "densities", "Density2D": "densities", "DensityND": "densities", "GridDensity": "densities",
     "DensitiesError": "densities", "getContourLevels": "densities", "nearestFFTnumber": "convolve",
     "loadMCSamples": "chainfiles", "chainFiles": "chainfiles", "prefill_plot_caches": "plotting",
 }

@@ -25,6 +25,7 @@ def run(mc, js, fine_bins, num_bins, smooth_scale_1D, bco, mbc, want_hist):
     """(P[B, F], hist[B, F] or None, meta[B, 9]) for the columns ``js`` (their parameters initialised by the caller)."""
     from . import mcsamples as M
     from ._lib import GdhipError
+    from .chains import MCSamplesError
 
     names = mc.paramNames.names
     s = Density1DSettings()
@@ -49,7 +50,7 @@ def run(mc, js, fine_bins, num_bins, smooth_scale_1D, bco, mbc, want_hist):
             if e.code == -5:
                 raise M.BandwidthError(_as_python_prints(_with_names(msg, names)))
             if "Parameter range is <= 0" in msg:
-                raise M.MCSamplesError("Parameter range is <= 0: " + names[int(msg.rsplit(" ", 1)[-1])].name)
+                raise MCSamplesError("Parameter range is <= 0: " + names[int(msg.rsplit(" ", 1)[-1])].name)
             if e.code == -1:
                 raise M.SettingError(msg)
             raise

@@ -143,7 +143,7 @@ def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None):
     Returns dict(samples=[per-chain (rows, n)], weights=[...], loglikes=[...], names, labels, derived, ranges,
     from_cache).  No burn-in is removed here.
     """
-    from .mcsamples import WeightedSampleError
+    from .chains import WeightedSampleError
 
     files = chainFiles(file_root, chain_exclude=chain_exclude) or chainFiles(file_root, separator=".", chain_exclude=chain_exclude)
     if not files:

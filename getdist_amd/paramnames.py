@@ -1,0 +1,120 @@
+"""
+Parameter names and per-parameter state: ``ParamInfo`` and ``ParamNames``, the parts of getdist/paramnames.py that
+the KDE / weighted-statistics path reads and writes.
+"""
+
+try:
+    # GetDist's plotting layer -- the caller this package is a drop-in for -- recognises a parameter object by
+    # isinstance(param, getdist.paramnames.ParamInfo) (plots.py:607,1981,2027).  Where GetDist is installed beside this
+    # package our parameter objects therefore derive from its class; without it they stand alone.
+    from getdist.paramnames import ParamInfo as _PlotParamInfo
+except Exception:  # noqa: BLE001 -- not installed (or not importable): nothing of the path needs it
+    _PlotParamInfo = object
+
+
+class ParamInfo(_PlotParamInfo):
+    """Per-parameter state bag; the attributes the hot path reads and writes (paramnames.py:69-154)."""
+
+    def __init__(self, name, label=None):
+        if _PlotParamInfo is not object:
+            super().__init__(name=name, label=label or name)
+        self.name = name
+        self.label = label or name
+        self.isDerived = False
+        self.limmin = self.limmax = None
+        self.has_limits_bot = self.has_limits_top = self.has_limits = False
+        self.periodic = False
+        self.N_eff_kde = None
+        self.kde_h = None
+        self.renames = []   # alternative names a caller may use for this parameter (paramnames.py:86)
+        self.comment = ""
+
+    def getLabel(self):
+        """paramnames.py:120-124"""
+        return self.label if self.label else self.name
+
+    def latexLabel(self):
+        """paramnames.py:126-130: what the plotting layer writes on an axis"""
+        return "$" + self.label + "$" if self.label else self.name
+
+    def __repr__(self):
+        return "ParamInfo(%s)" % self.name
+
+
+class ParamNames:
+    def __init__(self, names, labels=None):
+        labels = labels or [None] * len(names)
+        self.names = [ParamInfo(n, lab) for n, lab in zip(names, labels)]
+
+    def parWithName(self, name, error=False, renames=None):
+        """paramnames.py:232-255: the parameter called ``name`` -- by its own name, by one of its ``renames``, or through the
+        optional ``renames`` mapping {name: alternative name(s)} the plotting layer passes along."""
+        if not isinstance(name, str):
+            raise ValueError('"name" must be a parameter name string not %s: %s' % (type(name), name))
+
+        def alts(key):
+            v = renames.get(key, []) if renames else []
+            return [v] if isinstance(v, str) else list(v)
+
+        asked = {name, *alts(name)}
+        for p in self.names:
+            if asked & {p.name, *getattr(p, "renames", []), *alts(p.name)}:
+                return p
+        if error:
+            from .chains import ParamError  # (chains imports this module)
+
+            raise ParamError("parameter name not found: %s" % name)
+        return None
+
+    def hasParam(self, name):
+        return self.numberOfName(name) != -1
+
+    def getMatches(self, pattern, strings=False):
+        """paramnames.py:299-307: parameters whose name matches a shell-style pattern"""
+        import fnmatch
+
+        return [(p.name if strings else p) for p in self.names if fnmatch.fnmatchcase(p.name, pattern)]
+
+    def parsWithNames(self, names, error=False, renames=None):
+        """paramnames.py:273-297: ParamInfo per name (None where a name is unknown and ``error`` is false for it); names
+        holding * or ? expand to every match; ``error`` may be one flag or one per name."""
+        if isinstance(names, str):
+            names = [names]
+        flags = list(error) if isinstance(error, (list, tuple)) else [error]
+        if len(flags) < len(names):
+            flags = len(names) * flags
+        out = []
+        for nm, flag in zip(names, flags):
+            if isinstance(nm, ParamInfo):
+                out.append(nm)
+            elif "?" in nm or "*" in nm:
+                out += self.getMatches(nm)
+            else:
+                out.append(self.parWithName(nm, flag, renames))
+        return out
+
+    def getRenames(self, keep_empty=False):
+        """paramnames.py:324-332"""
+        return {p.name: list(getattr(p, "renames", [])) for p in self.names if keep_empty or getattr(p, "renames", [])}
+
+    def numParams(self):
+        return len(self.names)
+
+    def labels(self):
+        return [p.label for p in self.names]
+
+    def numberOfName(self, name):
+        for i, p in enumerate(self.names):
+            if p.name == name:
+                return i
+        return -1
+
+    def list(self):
+        return [p.name for p in self.names]
+
+    def numNonDerived(self):
+        return len([p for p in self.names if not p.isDerived])
+
+    def deleteIndices(self, indices):
+        gone = set(indices)
+        self.names = [p for i, p in enumerate(self.names) if i not in gone]

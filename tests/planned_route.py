@@ -9,9 +9,17 @@ of contexts that have no native entry (tests/fake_ctx.py: the CPU suite's host-l
 install() registers it as MCSamples._planned_route; tests/fake_ctx.py and tests/conftest.py call it.
 Follows getdist/mcsamples.py:1748-2010 (get2DDensityGridData) and :1285-1419 (getAutoBandwidth2D) of the reference.
 """
-from getdist_amd import mcsamples as _M
+import logging
+import os
+import threading
 
-globals().update({k: v for k, v in vars(_M).items() if not k.startswith("__")})  # the module's helpers, by their names
+import numpy as np
+
+from getdist_amd import mcsamples as _M
+from getdist_amd._lib import GdhipError
+from getdist_amd.chains import MCSamplesError
+from getdist_amd.densities import DensitiesError, Density2D
+from getdist_amd.mcsamples import SettingError, _hostlog, _Phase, _set_all_edge_mask_2d, _set_edge_mask_2d, next_fft_size
 
 
 class _PendingResults:
