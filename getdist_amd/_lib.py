@@ -150,6 +150,7 @@ SIGNATURES = {
     "gd_histnd_batch": (C.c_int, [_p, _i32, _pi32, _pi32, _pd, _pd, _i32, _i32, _i32, _pd, _pd, _pd]),
     "gd_pca_corr": (C.c_int, [_p, _pi32, _i32, _pi32, _pd, _pd, _pd]),
     "gd_pca_project": (C.c_int, [_p, _pi32, _i32, _pi32, _pd, _pd, _pd, _i32, _i32, _pd, _pd, _pd, _pd, _pd, _pd]),
+    "gd_mixture_nll": (C.c_int, [_p, _pi32, _i32, _i32, _pd, _pd, _pd, _i64, _i64, _pd]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
@@ -709,6 +710,20 @@ class Context:
                                             n_all, _dp(all_means), _dp(all_sd), _dp(newmean), _dp(newsd), _dp(pcpc),
                                             _dp(pcpar)))
         return newmean, newsd, pcpc, pcpar
+
+    def mixture_nll(self, cols, means, whiten, logcoef, lo=0, hi=None):
+        """-log pdf of a Gaussian mixture at the rows [lo, hi) of the resident columns ``cols`` (gd_mixture_nll):
+        ``means`` (K, d), ``whiten`` (K, d, d) lower-triangular inverse Cholesky factors of the covariances, ``logcoef`` (K)
+        = log(weight) - log(norm).  Returns a host float64 vector of hi - lo values (a view of page-locked memory)."""
+        cols, means, whiten, logcoef = _i32arr(cols), _f64arr(means), _f64arr(whiten), _f64arr(logcoef)
+        d, K = cols.size, logcoef.size
+        if means.shape != (K, d) or whiten.shape != (K, d, d):
+            raise ValueError("mixture_nll: inconsistent shapes")
+        hi = self.N if hi is None else int(hi)
+        out = self.pinned_array((max(hi - int(lo), 0),))
+        self._check(self.lib.gd_mixture_nll(self.h, _ip(cols), d, K, _dp(means), _dp(whiten), _dp(logcoef), int(lo), hi,
+                                            _dp(out)))
+        return out
 
     # ---- auxiliary vectors
     EXTRA_COLS = 4

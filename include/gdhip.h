@@ -466,6 +466,23 @@ int gd_pca_project(gd_ctx* ctx, const int32_t* cols, int32_t np, const int32_t* 
                    const double* U, int32_t doexp, int32_t n_all, const double* all_means, const double* all_sd,
                    double* newmean_out, double* newsd_out, double* pcpc_out, double* pcpar_out);
 
+/* ---------------------------------------------------------------- Gaussian mixtures -------------
+ * gd_mixture_nll: minus the log of a K-component, d-dimensional Gaussian-mixture density at every resident sample row of
+ *   [row_lo, row_hi) (gaussian_mixtures.MixtureND.logLikes, MixtureND.MCSamples(logLikes=True); the reference forms
+ *   -log(pdf) with one einsum per component, gaussian_mixtures.py:135-155):
+ *     out[r - row_lo] = -log sum_k exp(logcoef[k] - 1/2 |W_k (x_r - mu_k)|^2),   x_r = the columns cols[0..d) of row r,
+ *   mu_k = means[k d ..], W_k = whiten[k d d ..] row-major LOWER-TRIANGULAR (entries above the diagonal are not read) with
+ *   W_k = L_k^-1 for cov_k = L_k L_k^T, logcoef[k] = log(weight_k) - log(norm_k).  The sum over components is a max-shifted
+ *   log-sum-exp: the result stays finite where exp(-chi^2 / 2) underflows (chi^2 above ~1490).  Sample weights are not
+ *   involved.  The selected columns are read from HBM once for all K components (a block stages its rows' columns in LDS),
+ *   there is no N x d temporary, W and mu are read through the scalar cache, fp64 throughout with a summation order fixed
+ *   by (d, K): reruns are bit-identical.  `out` is host memory (page-locked for a full-rate copy).  Returns GD_ERR_BADARG,
+ *   before any launch, when no samples are uploaded, d is outside 1..uploaded columns (or above 1280: one 16-row tile of
+ *   d columns must fit in LDS), K < 1, a column index is out of range or the row range is empty or outside the sample set.
+ *   Blocks until the result is in `out`. */
+int gd_mixture_nll(gd_ctx* ctx, const int32_t* cols, int32_t d, int32_t K, const double* means, const double* whiten,
+                   const double* logcoef, int64_t row_lo, int64_t row_hi, double* out);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
