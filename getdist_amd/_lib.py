@@ -151,11 +151,14 @@ SIGNATURES = {
     "gd_pca_corr": (C.c_int, [_p, _pi32, _i32, _pi32, _pd, _pd, _pd]),
     "gd_pca_project": (C.c_int, [_p, _pi32, _i32, _pi32, _pd, _pd, _pd, _i32, _i32, _pd, _pd, _pd, _pd, _pd, _pd]),
     "gd_mixture_nll": (C.c_int, [_p, _pi32, _i32, _i32, _pd, _pd, _pd, _i64, _i64, _pd]),
+    "gd_draw_single_rows": (C.c_int, [_p, C.POINTER(C.c_uint64), _p, _f64, _f64, _i32, _p, _i64, _pi64]),
+    "gd_gather_rows": (C.c_int, [_p, _p, _i64, _pi32, _i32, _p]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
 GD_HISTND_H, GD_HISTND_LIKES, GD_HISTND_LMIN = 1, 2, 4
 GD_PCA_MAX_PROJ = 448
+GD_DRAW_MORE_ROWS = -21
 
 _lib = None
 
@@ -808,6 +811,59 @@ class Context:
         out = np.zeros((len(cols), int(maxoff)))
         self._check(self.lib.gd_thinned_lag_sums(self.h, _ip(cols), len(cols), _dp(means), rows.ptr, int(K), int(maxoff),
                                                  _dp(out)))
+        return out
+
+    # ---- weight-one sample draws
+    def draw_single_rows(self, a, b, mode=0, pcg=None, rand=None, capacity=None):
+        """Rows kept by a weight-one draw (gd_draw_single_rows): row i when rand_i <= w_i / (a * b) (mode 0) or
+        (w_i / a) / b (mode 1).  ``pcg`` = (state, inc), the two 128-bit integers of a PCG64 bit generator's state, draws the
+        variates on the device; ``rand`` (N doubles drawn on the host) is the route of every other generator.  Returns
+        (rows, K): a device int32 buffer with the K kept rows in ascending order.  ``capacity`` (default N, which always
+        fits) bounds the buffer; when the draw keeps more, nothing is written and (None, K) comes back."""
+        if (pcg is None) == (rand is None):
+            raise ValueError("draw_single_rows takes the PCG64 state or a vector of variates")
+        capacity = self.N if capacity is None else int(capacity)
+        st, d_rand = None, None
+        if pcg is not None:
+            m64 = (1 << 64) - 1
+            state, inc = int(pcg[0]), int(pcg[1])
+            st = (C.c_uint64 * 4)(state >> 64, state & m64, inc >> 64, inc & m64)
+        else:
+            rand = _f64arr(rand)
+            if rand.shape != (self.N,):
+                raise ValueError("one variate per sample row")
+            d_rand = self.alloc(rand.nbytes)
+            d_rand.from_host(rand)
+        buf = self.alloc(max(capacity, 1) * 4)
+        n = C.c_int64()
+        try:
+            rc = self.lib.gd_draw_single_rows(self.h, st, None if d_rand is None else d_rand.ptr, float(a), float(b), int(mode),
+                                              buf.ptr, capacity, C.byref(n))
+        finally:
+            if d_rand is not None:
+                d_rand.free()
+        if rc == GD_DRAW_MORE_ROWS:
+            buf.free()
+            return None, n.value
+        if rc != 0:
+            buf.free()
+        self._check(rc)
+        return buf, n.value
+
+    def gather_rows(self, rows, K, cols):
+        """(K, len(cols)) host array of the resident columns ``cols`` (any order, repeats allowed) at the K rows of the
+        device row list ``rows`` (gd_gather_rows)."""
+        cols = _i32arr(cols)
+        K = int(K)
+        out = np.empty((K, cols.size))
+        if cols.size == 0:
+            return out
+        d_out = self.alloc(max(out.nbytes, 8))
+        try:
+            self._check(self.lib.gd_gather_rows(self.h, rows.ptr, K, _ip(cols), cols.size, d_out.ptr))
+            self._check(self.lib.gd_memcpy_d2h(self.h, out.ctypes.data, d_out.ptr, out.nbytes))
+        finally:
+            d_out.free()
         return out
 
     # ---- mean likelihoods

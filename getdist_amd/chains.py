@@ -520,6 +520,54 @@ class WeightedSamples:
         buf.free()
         return out
 
+    # ---- weight-one random draws (chains.py:918-939; mcsamples.py:578-606) --------------------------------------
+    def _draw_single_rows(self, random_state, a, b, mode):
+        """
+        Device row list (buffer, count) of the rows a weight-one draw keeps: rand <= w / (a * b) (mode 0) or (w / a) / b
+        (mode 1), rand = np.random.default_rng(random_state).random(numrows) -- the reference's rows, bit for bit.  A PCG64
+        bit generator (numpy's default) hands its (state, inc) to the device, where every thread regenerates its rows'
+        variates (gd_draw_single_rows), and is moved numrows steps on; any other bit generator draws on the host and the
+        vector is uploaded.  Either way a Generator the caller passed in ends where the reference leaves it.
+        """
+        rng = np.random.default_rng(random_state)
+        bg = rng.bit_generator
+        if type(bg) is np.random.PCG64:
+            before = bg.state
+            source = dict(pcg=(before["state"]["state"], before["state"]["inc"]))
+            bg.advance(self.numrows)
+            if before["has_uint32"]:  # random() keeps a buffered 32-bit half, advance() drops it
+                after = bg.state
+                after["has_uint32"], after["uinteger"] = before["has_uint32"], before["uinteger"]
+                bg.state = after
+        else:
+            source = dict(rand=rng.random(self.numrows))
+        # room for the expected number of rows and eight standard deviations (Poisson-binomial: variance <= mean); the rare
+        # draw that keeps more reports its count and is repeated with exactly that room
+        with np.errstate(all="ignore"):
+            mean = float(self.norm) / (float(a) * float(b))
+        capacity = self.numrows
+        if np.isfinite(mean) and mean >= 0:
+            capacity = min(self.numrows, int(mean + 8 * np.sqrt(mean)) + 64)
+        buf, K = self.ctx.draw_single_rows(a, b, mode, capacity=capacity, **source)
+        if buf is None:
+            buf, K = self.ctx.draw_single_rows(a, b, mode, capacity=K, **source)
+        return buf, K
+
+    def random_single_samples_indices(self, random_state=None, thin=None, max_samples=None):
+        """chains.py:918-939: indices of a weight-one subset, each row kept with probability weight / (max weight * thin);
+        the same rows as the reference for the same ``random_state`` (seed, Generator or bit generator).  ``max_samples``
+        thins to that mean number of rows instead.  The draw and the ordered compaction run on the device."""
+        if max_samples is None:
+            thin = thin or 1
+        else:
+            if thin is not None:
+                raise WeightedSampleError("Cannot set thin and max_samples")
+            thin = max(1, self.norm / self.max_mult / max_samples)
+        buf, K = self._draw_single_rows(random_state, self.max_mult, thin, 0)
+        out = buf.to_host((K,), dtype=np.int32).astype(np.int64) if K else np.zeros(0, dtype=np.int64)
+        buf.free()
+        return out
+
     # ---- autocorrelation / effective samples (chains.py:423-574) -------------------------------------------
     DIRECT_LAGS_MAX = 512  # beyond this many lags the length-2N FFT (gd_autoconvolve) is cheaper than lag sums
 

@@ -572,6 +572,34 @@ class MCSamples(Chains):
         finally:
             self.ctx.select_weights(0)
 
+    def makeSingleSamples(self, filename="", single_thin=None, random_state=None):
+        """
+        mcsamples.py:578-606: unit-weight samples, each row chosen with probability weight / (max weight * single_thin);
+        the same rows as the reference for the same ``random_state``.  ``single_thin`` defaults to what leaves about
+        max_scatter_points rows.  Without ``filename`` the kept rows are gathered on the device (gd_gather_rows) and
+        returned as a (K, n) array; with it they are written as text (weight 1, loglike, parameters) and nothing is
+        returned -- that branch divides in the reference's other order, (weight / max weight) / single_thin.
+        """
+        if single_thin is None:
+            single_thin = max(1, self.norm / self.max_mult / self.max_scatter_points)
+        if not filename:
+            buf, K = self._draw_single_rows(random_state, self.max_mult, single_thin, 0)
+            try:
+                return self.ctx.gather_rows(buf, K, np.arange(self.n))
+            finally:
+                buf.free()
+        if self.loglikes is None:
+            raise MCSamplesError("writing single samples needs the loglikes column")
+        buf, K = self._draw_single_rows(random_state, self.max_mult, single_thin, 1)
+        rows = buf.to_host((K,), dtype=np.int32) if K else np.zeros(0, dtype=np.int32)
+        buf.free()
+        with open(filename, "w", encoding="utf-8") as f:
+            for i in rows:
+                f.write("%16.7E" % 1.0)
+                f.write("%16.7E" % (self.loglikes[i]))
+                f.writelines("%16.7E" % v for v in self.samples[i])
+                f.write("\n")
+
     def getFractionIndices(self, weights, n):
         """mcsamples.py:668-680: row indices splitting the total weight into n equal parts"""
         if weights is None:

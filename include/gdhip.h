@@ -483,6 +483,30 @@ int gd_pca_project(gd_ctx* ctx, const int32_t* cols, int32_t np, const int32_t* 
 int gd_mixture_nll(gd_ctx* ctx, const int32_t* cols, int32_t d, int32_t K, const double* means, const double* whiten,
                    const double* logcoef, int64_t row_lo, int64_t row_hi, double* out);
 
+/* ---------------------------------------------------------------- weight-one sample draws -------
+ * gd_draw_single_rows: the rows that makeSingleSamples (mcsamples.py:578-606) and random_single_samples_indices
+ *   (chains.py:918-939) keep: row i of the resident sample set is kept when  rand_i <= threshold_i,  with the sample weight
+ *   w_i (1 when the set is unweighted; the sample weights also while auxiliary weights are selected) and
+ *     mode 0: threshold_i = w_i / (a * b)     (the array branch, mcsamples.py:606, and chains.py:939)
+ *     mode 1: threshold_i = (w_i / a) / b     (the file branch, mcsamples.py:600)
+ *   in IEEE fp64 with exactly these operations (the two orders round differently, and both are the reference's).
+ *   rand is np.random.default_rng(random_state).random(N): either pcg_state = {state_hi, state_lo, inc_hi, inc_lo}, the two
+ *   128-bit words of a PCG64 bit_generator.state["state"], from which every thread regenerates its rows' variates bit for bit
+ *   (csrc/pcg64.hpp; the generator itself is then N steps further: bit_generator.advance(N)), or d_rand, a device vector
+ *   of N doubles drawn on the host by any other bit generator -- exactly one of the two is given.
+ *   d_rows (device, `capacity` int32 entries) receives the kept row numbers in ascending order and *count_out their count
+ *   K.  Nothing is written at or beyond `capacity`: when K > capacity the call writes no row, sets *count_out = K and
+ *   returns GD_DRAW_MORE_ROWS; call again with room for K.  GD_ERR_BADARG when no samples are uploaded, both or neither
+ *   source of variates is given, the mode is unknown, or the set has 2^31 rows or more (row numbers are int32).  Two reads
+ *   of the weights, no N-sized temporary.  Blocks until the list is complete.
+ * gd_gather_rows: d_out (device, K x m fp64, row-major) = the resident columns cols[0..m) (any order, repeats allowed;
+ *   spare columns included) at the rows of the device list d_rows (K int32); a row number outside the sample set gives NaN.
+ *   K = 0 does nothing.  Blocks until d_out is written. */
+#define GD_DRAW_MORE_ROWS (-21)
+int gd_draw_single_rows(gd_ctx* ctx, const uint64_t* pcg_state, const void* d_rand, double a, double b, int32_t mode,
+                        void* d_rows, int64_t capacity, int64_t* count_out);
+int gd_gather_rows(gd_ctx* ctx, const void* d_rows, int64_t K, const int32_t* cols, int32_t m, void* d_out);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
