@@ -153,12 +153,22 @@ SIGNATURES = {
     "gd_mixture_nll": (C.c_int, [_p, _pi32, _i32, _i32, _pd, _pd, _pd, _i64, _i64, _pd]),
     "gd_draw_single_rows": (C.c_int, [_p, C.POINTER(C.c_uint64), _p, _f64, _f64, _i32, _p, _i64, _pi64]),
     "gd_gather_rows": (C.c_int, [_p, _p, _i64, _pi32, _i32, _p]),
+    "gd_format_rows": (C.c_int, [_p, _pi32, _i32, _i64, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _i64, _pi64]),
+    "gd_format_matrix": (C.c_int, [_p, _p, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _p, _i64, _pi64]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
 GD_HISTND_H, GD_HISTND_LIKES, GD_HISTND_LMIN = 1, 2, 4
 GD_PCA_MAX_PROJ = 448
 GD_DRAW_MORE_ROWS = -21
+GD_FORMAT_MORE_BYTES = -22
+GD_FMT_SRC_WEIGHT, GD_FMT_SRC_ZERO, GD_FMT_SRC_ONE = -1, -2, -3
+GD_FMT_MAX_PREC, GD_FMT_MAX_WIDTH = 17, 32
+
+
+def format_field_bytes(width, prec):
+    """Upper bound of one formatted field, separator or newline included (gd_format_rows / gd_format_matrix)."""
+    return max(int(width), int(prec) + 8) + 1
 
 _lib = None
 
@@ -865,6 +875,75 @@ class Context:
         finally:
             d_out.free()
         return out
+
+    # ---- chain export
+    def _format_finish(self, call, rows, m, width, prec, out, host):
+        need = max(int(rows) * int(m) * format_field_bytes(width, prec), 1)
+        buf = self.alloc(need) if out is None else out
+        n = C.c_int64()
+        rc = call(buf.ptr, int(buf.nbytes), C.byref(n))
+        if rc == GD_FORMAT_MORE_BYTES:  # only a caller-supplied buffer can be too small
+            return None, n.value
+        if rc != 0 and out is None:
+            buf.free()
+        self._check(rc)
+        if host is not None and n.value:
+            view = np.asarray(host).reshape(-1).view(np.uint8)
+            if view.size < n.value:
+                raise ValueError("host buffer holds %d bytes, the text takes %d" % (view.size, n.value))
+            self._check(self.lib.gd_memcpy_d2h(self.h, view.ctypes.data, buf.ptr, n.value))
+        return buf, n.value
+
+    def format_rows(self, srcs, lo=None, hi=None, rows=None, K=None, row_offset=0, width=0, prec=8, upper=False, sep=True,
+                    out=None, host=None):
+        """Text of sample rows as np.savetxt(fmt="%W.Pe") writes it (gd_format_rows): field j is the resident column
+        srcs[j] (spare columns included), GD_FMT_SRC_WEIGHT, GD_FMT_SRC_ZERO or GD_FMT_SRC_ONE; the rows are [lo, hi) or the K
+        rows of the device int32 list ``rows`` from entry ``row_offset`` on.  Returns (device buffer, bytes); ``out`` supplies the buffer (when it is too
+        small nothing is written and (None, bytes needed) comes back), ``host`` (page-locked uint8) also receives the text."""
+        srcs = _i32arr(srcs)
+        if (rows is None) == (lo is None):
+            raise ValueError("format_rows takes a row interval or a device row list")
+        if rows is None:
+            nrows, sel = int(hi) - int(lo), (int(lo), int(hi), None, 0)
+        else:
+            nrows, sel = int(K), (0, 0, rows.ptr + 4 * int(row_offset), int(K))
+
+        def call(ptr, cap, n):
+            return self.lib.gd_format_rows(self.h, _ip(srcs), srcs.size, sel[0], sel[1], sel[2], sel[3], int(width), int(prec),
+                                           int(bool(upper)), int(bool(sep)), ptr, cap, n)
+
+        return self._format_finish(call, max(nrows, 0), srcs.size, width, prec, out, host)
+
+    def format_matrix(self, x, width=0, prec=8, upper=False, sep=True, out=None, host=None, shape=None, strides=None):
+        """Text of a 2D fp64 matrix (gd_format_matrix).  ``x`` is a host array (uploaded here) or a device buffer with
+        ``shape`` = (K, m) and ``strides`` = (row, column) in elements.  Returns (device buffer, bytes) as format_rows."""
+        tmp = None
+        if isinstance(x, DevBuf) or shape is not None:
+            (K, m), (rs, cs), src = shape, strides, x
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float64)
+            if x.ndim != 2:
+                raise ValueError("format_matrix takes a 2D array")
+            (K, m), (rs, cs) = x.shape, (x.shape[1], 1)
+            tmp = src = self.alloc(max(x.nbytes, 8))
+            src.from_host(x)
+        ptr0 = src.ptr
+
+        def call(ptr, cap, n):
+            return self.lib.gd_format_matrix(self.h, ptr0 if K else None, int(K), int(m), int(rs), int(cs), int(width), int(prec),
+                                             int(bool(upper)), int(bool(sep)), ptr, cap, n)
+
+        try:
+            return self._format_finish(call, K, m, width, prec, out, host)
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def fetch_bytes_async(self, buf, host, nbytes):
+        """Start the copy of the first ``nbytes`` of a device buffer into the page-locked uint8 array ``host`` on the copy
+        stream (ordered after the compute stream's work so far); copy_mark() / copy_wait() tell when it has landed."""
+        if nbytes:
+            self._check(self.lib.gd_memcpy_d2h_async(self.h, host.ctypes.data, buf.ptr, int(nbytes)))
 
     # ---- mean likelihoods
     def like_weights(self, loglikes, mode, mean_loglike):

@@ -6,6 +6,9 @@ MCSamples.  Follows chains.py:77-125 (file matching, loadNumpyTxt), chains.py:22
 (ignore_rows burn-in per chain, fixed-parameter deletion, makeSingle) and paramnames.py / parampriors.py for the two
 side files.  The parse itself is host work (pandas' C tokenizer when present: ~10x np.loadtxt); the columns go to the
 device in the same SoA layout as array input.
+
+Chain export is the way back: ``write_text_rows`` streams rows of the resident sample set into a text file whose bytes are
+np.savetxt's, formatted on the device (gd_format_rows) in chunks that overlap the file writes.
 """
 
 import os
@@ -57,9 +60,10 @@ def loadNumpyTxt(fname, skiprows=None):
         raise
 
 
-def readParamNames(fname):
-    """paramnames.py:95-110, 250-270: (names, labels, derived flags) of a .paramnames file."""
-    names, labels, derived = [], [], []
+def readParamNames(fname, with_comments=False):
+    """paramnames.py:97-111, 250-270: (names, labels, derived flags[, comments]) of a .paramnames file; what follows a
+    ``#`` on a line is the parameter's comment (ParamInfo.string writes it there), not part of the label."""
+    names, labels, derived, comments = [], [], [], []
     with open(fname, encoding="utf-8-sig") as f:
         for line in f:
             line = line.strip()
@@ -70,8 +74,10 @@ def readParamNames(fname):
             is_derived = name.endswith("*")
             names.append(name[:-1] if is_derived else name)
             derived.append(is_derived)
-            labels.append(parts[1].strip() if len(parts) > 1 else None)
-    return names, labels, derived
+            label, _, comment = parts[1].partition("#") if len(parts) > 1 else ("", "", "")
+            labels.append(label.strip() or None)
+            comments.append(comment.strip())
+    return (names, labels, derived, comments) if with_comments else (names, labels, derived)
 
 
 def readRanges(fname):
@@ -84,6 +90,181 @@ def readRanges(fname):
                 lo, hi = (None if v in ("N", "None") else float(v) for v in parts[1:3])
                 ranges[parts[0]] = (lo, hi)
     return ranges
+
+
+TEXT_CHUNK_BYTES = 192 << 20  # text per chunk of write_text_rows: two device and two page-locked blocks of this size
+_DEVICE_SPEC = re.compile(r"%([1-9][0-9]*)?(?:\.([0-9]+))?([eE])")
+_host_route_logged = set()
+
+
+def parse_device_format(fmt):
+    """(width, prec, upper) when ``fmt`` is one ``%[width][.prec](e|E)`` conversion without flags, inside the range the
+    device formats (width <= 32, prec <= 17; no precision means 6, as in C) -- ``"%.8e"`` (chains.py:227) and ``"%16.7E"``
+    (mcsamples.py:598) among them; None for anything else (%f, %g, flags, a list of formats), which np.savetxt formats
+    on the host."""
+    from ._lib import GD_FMT_MAX_PREC, GD_FMT_MAX_WIDTH
+
+    m = _DEVICE_SPEC.fullmatch(fmt) if isinstance(fmt, str) else None
+    if m is None:
+        return None
+    width, prec = int(m.group(1) or 0), 6 if m.group(2) is None else int(m.group(2))
+    if width > GD_FMT_MAX_WIDTH or prec > GD_FMT_MAX_PREC:
+        return None
+    return width, prec, m.group(3) == "E"
+
+
+def _write_rows_host(f, rows, fmt, delimiter, host_rows, why):
+    """The documented host route: np.savetxt of the rows gathered on the host -- the reference's own code path."""
+    import logging
+
+    if why not in _host_route_logged:
+        _host_route_logged.add(why)
+        logging.getLogger(__name__).info("chain text is formatted on the host by np.savetxt: %s", why)
+    if isinstance(rows[0], (int, np.integer)):
+        index = slice(int(rows[0]), int(rows[1]))
+    else:
+        buf, K = rows
+        index = buf.to_host((K,), dtype=np.int32).astype(np.int64) if K else np.zeros(0, dtype=np.int64)
+    np.savetxt(f, host_rows(index), fmt=fmt, delimiter=delimiter)
+
+
+def _write_rows_device(f, ctx, srcs, rows, spec, sep, chunk_rows):
+    import queue
+    import threading
+
+    from ._lib import format_field_bytes
+
+    width, prec, upper = spec
+    contiguous = isinstance(rows[0], (int, np.integer))
+    total = int(rows[1]) - int(rows[0]) if contiguous else int(rows[1])
+    if total <= 0:
+        return
+    per_row = len(srcs) * format_field_bytes(width, prec)
+    chunk_rows = int(chunk_rows) if chunk_rows else max(1, TEXT_CHUNK_BYTES // per_row)
+    chunk_rows = min(chunk_rows, total)
+    nbuf = 2 if total > chunk_rows else 1
+    dev = [ctx.alloc(chunk_rows * per_row) for _ in range(nbuf)]
+    host = [ctx.pinned_array((chunk_rows * per_row,), np.uint8) for _ in range(nbuf)]
+    free, todo, failed = queue.Queue(), queue.Queue(), []
+    for b in range(nbuf):
+        free.put(b)
+
+    def drain():  # waits for a chunk's copy and writes it while the next chunk is formatted and copied
+        ctx.bind_thread()
+        while True:
+            item = todo.get()
+            if item is None:
+                return
+            b, nbytes, mark = item
+            try:
+                if not failed:
+                    ctx.copy_wait(mark)
+                    f.write(memoryview(host[b])[:nbytes])
+            except BaseException as e:  # noqa: BLE001 -- handed to the caller's thread below
+                failed.append(e)
+            finally:
+                free.put(b)
+
+    writer = threading.Thread(target=drain, name="getdist_amd-text-writer")
+    writer.start()
+    try:
+        for start in range(0, total, chunk_rows):
+            b = free.get()
+            if failed:
+                break
+            k = min(chunk_rows, total - start)
+            if contiguous:
+                _, nbytes = ctx.format_rows(srcs, lo=int(rows[0]) + start, hi=int(rows[0]) + start + k, width=width, prec=prec,
+                                            upper=upper, sep=sep, out=dev[b])
+            else:
+                _, nbytes = ctx.format_rows(srcs, rows=rows[0], K=k, row_offset=start, width=width, prec=prec, upper=upper,
+                                            sep=sep, out=dev[b])
+            ctx.fetch_bytes_async(dev[b], host[b], nbytes)
+            todo.put((b, nbytes, ctx.copy_mark()))
+    finally:
+        todo.put(None)
+        writer.join()
+        for d in dev:
+            d.free()
+    if failed:
+        raise failed[0]
+
+
+def write_text_rows(path_or_file, ctx, srcs, rows, fmt="%.8e", delimiter=" ", chunk_rows=None, host_rows=None):
+    """
+    np.savetxt(path_or_file, <rows of the resident sample set>, fmt=fmt, delimiter=delimiter) without the host loop
+    (chains.py:1081-1085: one Python ``%`` per number there).  Field j of a row is ``srcs[j]``: a resident column (spare
+    columns included) or one of the GD_FMT_SRC_* codes of gd_format_rows; ``rows`` is ``(lo, hi)`` or ``(device int32 row
+    list, K)``.  The text is formatted on the device in chunks of ``chunk_rows`` rows (default: TEXT_CHUNK_BYTES of text)
+    into two device blocks, copied into two page-locked blocks on the copy stream and written by a helper thread, so the
+    ``file.write`` of one chunk overlaps the kernels and the copy of the next.  Zero rows give an empty file.
+
+    A path is written as ``path + ".tmp<pid>"`` and renamed when complete (as write_soa_cache): an interrupted save leaves
+    no truncated chain that a later load would take for a whole one.  An open binary file is written in place.
+
+    Host route: a format the device does not take (parse_device_format), a delimiter other than "" / " ", or a context
+    that cannot format (the numpy test double of the CPU tier) is written by np.savetxt itself from ``host_rows(index)``,
+    the (rows, m) host array of a slice or an index array; one logging line says so.
+    """
+    spec = parse_device_format(fmt)
+    why = None
+    if spec is None:
+        why = "format %r is not a single %%[width][.prec]e conversion" % (fmt,)
+    elif delimiter not in ("", " "):
+        why = "delimiter %r" % (delimiter,)
+    elif not hasattr(ctx, "format_rows"):
+        why = "the context has no device formatter"
+    if why is not None and host_rows is None:
+        raise ValueError("cannot write rows on the host route (%s) without host_rows" % why)
+
+    def body(f):
+        if why is not None:
+            _write_rows_host(f, rows, fmt, delimiter, host_rows, why)
+        else:
+            _write_rows_device(f, ctx, srcs, rows, spec, delimiter == " ", chunk_rows)
+
+    if hasattr(path_or_file, "write"):
+        body(path_or_file)
+        return
+    path = os.fspath(path_or_file)
+    tmp = path + ".tmp%d" % os.getpid()
+    try:
+        with open(tmp, "wb") as f:
+            body(f)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def read_properties(fname):
+    """The flat ``key=value`` lines of a .properties.ini (inifile.py:70-105 without includes): {key: value string}."""
+    params = {}
+    with open(fname, encoding="utf-8-sig") as f:
+        for line in f:
+            s = line.strip()
+            if s == "END":
+                break
+            if not s or s.startswith("#"):
+                continue
+            eq = s.find("=")
+            if eq >= 0:
+                params[s[:eq].strip()] = s[eq + 1:].strip()
+    return params
+
+
+def write_properties(fname, params, read_order=()):
+    """inifile.py:130-166 for a file without includes: ``key=value`` lines -- first the keys of ``read_order`` (the order
+    of the file the values were read from), then the others sorted -- joined by newlines without a trailing one,
+    booleans as T / F."""
+    def text(v):
+        return v if isinstance(v, str) else str(v)[0] if isinstance(v, bool) else str(v)
+
+    keys = [k for k in read_order if k in params]
+    keys += sorted(k for k in params if k not in keys)
+    with open(fname, "w", encoding="utf-8") as f:
+        f.write("\n".join(k + "=" + text(params[k]) for k in keys))
 
 
 CACHE_MAGIC = b"GDAMDSOA1\n"
@@ -176,16 +357,16 @@ def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None):
             except OSError:
                 pass  # read-only chain directory: the cache is an optimisation only
     n = chains[0].shape[1] - 2
-    labels = derived = None
+    labels = derived = comments = None
     if os.path.isfile(file_root + ".paramnames"):
-        names, labels, derived = readParamNames(file_root + ".paramnames")
+        names, labels, derived, comments = readParamNames(file_root + ".paramnames", with_comments=True)
         if len(names) != n:
             raise WeightedSampleError("paramnames file does not match the number of chain columns")
     else:
         names = ["param%d" % (i + 1) for i in range(n)]
     ranges = readRanges(file_root + ".ranges") if os.path.isfile(file_root + ".ranges") else {}
     return dict(samples=[c[:, 2:] for c in chains], weights=[c[:, 0] for c in chains], loglikes=[c[:, 1] for c in chains],
-                names=names, labels=labels, derived=derived, ranges={k: v for k, v in ranges.items() if k in names},
+                names=names, labels=labels, derived=derived, comments=comments, ranges={k: v for k, v in ranges.items() if k in names},
                 from_cache=from_cache)
 
 

@@ -9,6 +9,7 @@ Neither class has a constructor of its own: ``mcsamples.MCSamples`` builds the o
 """
 
 import logging
+import os
 import threading
 
 import numpy as np
@@ -270,6 +271,41 @@ class WeightedSamples:
             return self.label
         name = self.getName()
         return None if name is None else "".join("\\" + ch if ch in "_&%$#{}" else ch for ch in name)
+
+    # ---- text export (chains.py:227, 1063-1085) --------------------------------------------------------------
+    precision = "%.8e"  # chains.py:227: the format of saveAsText
+
+    def _text_sources(self):
+        """(field sources of gd_format_rows, host_rows) for the rows of a chain file: weight, -log(posterior) (zeros when
+        there are no loglikes, chains.py:1072-1075), parameters.  The loglikes go into a spare device column; ``host_rows``
+        is the same table from the host arrays, for a ``precision`` the device does not format."""
+        from ._lib import GD_FMT_SRC_WEIGHT, GD_FMT_SRC_ZERO
+
+        ll = GD_FMT_SRC_ZERO if self.loglikes is None else self.ctx.set_extra_column(self.ctx.EXTRA_COLS - 1, self.loglikes)
+
+        def host_rows(index):
+            w = self._host_weights()[index]
+            loglikes = np.zeros(len(w)) if self.loglikes is None else self.loglikes[index]
+            return np.hstack((w.reshape(-1, 1), loglikes.reshape(-1, 1), self.samples[index]))
+
+        return [GD_FMT_SRC_WEIGHT, ll] + list(range(self.n)), host_rows
+
+    def _save_rows_as_text(self, root, chain_index, make_dirs, lo, hi, precision, sources=None):
+        """chains.py:1076-1085 for rows [lo, hi) of the resident set, formatted on the device (chainfiles.write_text_rows)"""
+        from . import chainfiles
+
+        if make_dirs and not os.path.exists(os.path.dirname(root)):
+            os.makedirs(os.path.dirname(root))
+        if root.endswith(".txt"):
+            root = root[:-3]  # (the reference's slice: the dot stays)
+        srcs, host_rows = sources or self._text_sources()
+        chainfiles.write_text_rows(root + ("" if chain_index is None else "_" + str(chain_index + 1)) + ".txt", self.ctx, srcs,
+                                   (int(lo), int(hi)), fmt=precision, host_rows=host_rows)
+
+    def saveAsText(self, root, chain_index=None, make_dirs=False):
+        """chains.py:1063-1085: the samples as ``root[_<chain_index + 1>].txt`` with columns weight, -log(posterior),
+        parameters in the format ``self.precision`` -- the bytes np.savetxt writes, formatted on the device."""
+        self._save_rows_as_text(root, chain_index, make_dirs, 0, self.numrows, self.precision)
 
     # ---- moments (chains.py:339-412, 636-780) ------------------------------------------------------------
     # Vectors, row filters and alternative weights (chains.py:325-337, 636-780): a host vector goes into one of the
@@ -838,6 +874,17 @@ class Chains(WeightedSamples):
         self._replace_samples(new, self.weights, self.loglikes, self.chain_offsets)
         return par
 
+    # ---- text export (chains.py:1562-1581) -------------------------------------------------------------------
+    def saveAsText(self, root, chain_index=None, make_dirs=False):
+        """chains.py:1562-1573: the chain file, and the metadata files unless a chain index above 0 is given"""
+        super().saveAsText(root, chain_index, make_dirs)
+        if not chain_index:
+            self.saveTextMetadata(root)
+
+    def saveTextMetadata(self, root):
+        """chains.py:1575-1581"""
+        self.paramNames.saveAsText(root + ".paramnames")
+
     # ---- what GetDist's plotting layer asks a sample set for besides densities (plots.py:655-690,933-955,2262-2290) ------
     def getParamNames(self):
         """chains.py:1221-1225"""
@@ -1220,6 +1267,12 @@ class ChainView:
     weights = property(lambda self: (np.ones(self.numrows) if self.parent.weights is None
                                      else self.parent.weights[self.lo:self.hi]))
     loglikes = property(lambda self: None if self.parent.loglikes is None else self.parent.loglikes[self.lo:self.hi])
+
+    precision = "%.8e"  # a separate chain is a plain WeightedSamples in the reference: the class default (chains.py:227)
+
+    def saveAsText(self, root, chain_index=None, make_dirs=False, _sources=None):
+        """chains.py:1063-1085 over this chain's rows of the resident set: no copy of the chain, no metadata files"""
+        self.parent._save_rows_as_text(root, chain_index, make_dirs, self.lo, self.hi, self.precision, _sources)
 
     def _weight_stats(self):
         if self._ws is None:

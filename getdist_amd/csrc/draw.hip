@@ -8,10 +8,11 @@
 //
 // Ordered compaction: a block owns a tile of DRAW_TILE consecutive rows and its threads walk it strided (lane-consecutive
 // rows: coalesced weight reads, one multiply-add of the 256-step map per row); pass 1 counts the kept rows of every tile,
-// one block scans the tile counts, pass 2 recomputes the flags and writes each kept row at tile offset + rank inside the
+// one block scans the tile counts (tilescan.hpp), pass 2 recomputes the flags and writes each kept row at tile offset + rank inside the
 // tile (ballots per wave and item round).  The list comes out ascending, as np.nonzero gives it.
 #include "ctx.hpp"
 #include "pcg64.hpp"
+#include "tilescan.hpp"
 
 #define DRAW_THREADS 256
 #define DRAW_ITEMS 8
@@ -64,31 +65,6 @@ __global__ void __launch_bounds__(DRAW_THREADS) k_draw_count(DrawArgs p, long lo
         for (int i = 0; i < DRAW_WAVES; ++i) t += red[i];
         tile_cnt[blockIdx.x] = t;
     }
-}
-
-// exclusive scan of the nb tile counts in place, 1024 per pass of one block; cnt[nb] receives the total
-__global__ void __launch_bounds__(1024) k_draw_scan(long long* __restrict__ cnt, int nb) {
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < nb; c0 += 1024) {
-        const int i = c0 + threadIdx.x;
-        const long long v = (i < nb) ? cnt[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const long long a = (threadIdx.x >= (unsigned)o) ? sh[threadIdx.x - o] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (i < nb) cnt[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) cnt[nb] = carry;
 }
 
 __global__ void __launch_bounds__(DRAW_THREADS) k_draw_write(DrawArgs p, const long long* __restrict__ tile_off,
@@ -158,7 +134,7 @@ int gd_draw_single_rows(gd_ctx* ctx, const uint64_t* pcg_state, const void* d_ra
     p.a = a, p.b = b, p.mode = mode;
     k_draw_count<<<nb, DRAW_THREADS, 0, ctx->stream>>>(p, cnt);
     GD_KERNEL_CHECK();
-    k_draw_scan<<<1, 1024, 0, ctx->stream>>>(cnt, nb);
+    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(cnt, nb);
     GD_KERNEL_CHECK();
     long long total = 0;
     GD_TRY(gd_fetch(ctx, &total, cnt + nb, 8));

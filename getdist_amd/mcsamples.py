@@ -252,6 +252,7 @@ class MCSamples(Chains):
         self._likeStats = None
         self._loglikes_col = None
         self.label, self.name_tag = label, name_tag
+        self.properties = None  # mcsamples.py:243: {key: value} (or an object with .params) saved to root.properties.ini
         self.root = root
         self.rootdirname = ""  # mcsamples.py:244: the output root of writeDataToFile (PCA writes rootdirname + ".PCA")
         self.raise_on_bandwidth_errors = False
@@ -278,7 +279,7 @@ class MCSamples(Chains):
         if self.sampler == "nested" and not np.isclose(self.ignore_rows, 0):
             raise ValueError("Should not remove burn-in from Nested Sampler samples.")
         self.ranges = ParamBounds()
-        derived = None
+        derived = comments = None
         if root is not None and samples is None:
             # mcsamples.py:47-146, chains.py:1368-1405: the chain files, side files and (when fresh) the binary cache
             from . import chainfiles
@@ -289,7 +290,7 @@ class MCSamples(Chains):
             samples, weights, loglikes = loaded["samples"], loaded["weights"], loaded["loglikes"]
             names = names or loaded["names"]
             labels = labels or loaded["labels"]
-            derived = loaded["derived"]
+            derived, comments = loaded["derived"], loaded.get("comments")
             for nm, rng in loaded["ranges"].items():
                 self.ranges.setRange(nm, rng)
             self.name_tag = self.name_tag or os.path.basename(root)
@@ -312,6 +313,9 @@ class MCSamples(Chains):
         if derived is not None:
             for par, d in zip(self.paramNames.names, derived):
                 par.isDerived = bool(d)
+        if comments is not None:
+            for par, c in zip(self.paramNames.names, comments):
+                par.comment = c
         for ix, value in fixed:  # chains.py:1555-1559: a parameter that never moves becomes a zero-width range
             self.ranges.setFixed(self.paramNames.names[ix].name, value)
         self.paramNames.deleteIndices([ix for ix, _ in fixed])
@@ -577,8 +581,8 @@ class MCSamples(Chains):
         mcsamples.py:578-606: unit-weight samples, each row chosen with probability weight / (max weight * single_thin);
         the same rows as the reference for the same ``random_state``.  ``single_thin`` defaults to what leaves about
         max_scatter_points rows.  Without ``filename`` the kept rows are gathered on the device (gd_gather_rows) and
-        returned as a (K, n) array; with it they are written as text (weight 1, loglike, parameters) and nothing is
-        returned -- that branch divides in the reference's other order, (weight / max weight) / single_thin.
+        returned as a (K, n) array; with it they are formatted on the device (gd_format_rows) and written as text
+        (weight 1, loglike, parameters), and nothing is returned -- that branch divides in the reference's other order, (weight / max weight) / single_thin.
         """
         if single_thin is None:
             single_thin = max(1, self.norm / self.max_mult / self.max_scatter_points)
@@ -591,14 +595,63 @@ class MCSamples(Chains):
         if self.loglikes is None:
             raise MCSamplesError("writing single samples needs the loglikes column")
         buf, K = self._draw_single_rows(random_state, self.max_mult, single_thin, 1)
-        rows = buf.to_host((K,), dtype=np.int32) if K else np.zeros(0, dtype=np.int32)
-        buf.free()
-        with open(filename, "w", encoding="utf-8") as f:
-            for i in rows:
-                f.write("%16.7E" % 1.0)
-                f.write("%16.7E" % (self.loglikes[i]))
-                f.writelines("%16.7E" % v for v in self.samples[i])
-                f.write("\n")
+        try:
+            # weight 1, loglike, parameters as "%16.7E" with nothing between the fields (mcsamples.py:596-601), formatted
+            # on the device from the row list the draw left there
+            from . import chainfiles
+            from ._lib import GD_FMT_SRC_ONE
+
+            srcs = [GD_FMT_SRC_ONE, self.ctx.set_extra_column(self.ctx.EXTRA_COLS - 1, self.loglikes)] + list(range(self.n))
+
+            def host_rows(index):
+                return np.hstack((np.ones((len(index), 1)), self.loglikes[index].reshape(-1, 1), self.samples[index]))
+
+            with open(filename, "wb") as f:
+                chainfiles.write_text_rows(f, self.ctx, srcs, (buf, K), fmt="%16.7E", delimiter="", host_rows=host_rows)
+        finally:
+            buf.free()
+
+    # ---- text export (mcsamples.py:637-666, 2662-2693) -------------------------------------------------------
+    def saveTextMetadata(self, root, properties=None):
+        """mcsamples.py:2662-2684: ``root.paramnames``, ``root.ranges`` and ``root.properties.ini`` -- the keys of an existing
+        file, then ``self.properties``, the label and ``properties``; the file is removed when there is nothing to say."""
+        from . import chainfiles
+
+        super().saveTextMetadata(root)
+        self.ranges.saveToFile(root + ".ranges")
+        ini_name = root + ".properties.ini"
+        own = getattr(self.properties, "params", self.properties)
+        if properties or own or self.label:
+            params = chainfiles.read_properties(ini_name) if os.path.exists(ini_name) else {}
+            read_order = list(params)
+            params.update(own or {})
+            if self.label:
+                params["label"] = self.label
+            params.update(properties or {})
+            chainfiles.write_properties(ini_name, params, read_order)
+        elif os.path.exists(ini_name):
+            os.remove(ini_name)
+
+    def saveChainsAsText(self, root, make_dirs=False, properties=None):
+        """mcsamples.py:2686-2693: ``root_1.txt, root_2.txt, ...``, one per chain of getSeparateChains (row ranges of the
+        resident set: what thin / filter / reweighting left there is what is saved), then the metadata files."""
+        sources = self._text_sources()
+        for i, chain in enumerate(self.getSeparateChains()):
+            chain.saveAsText(root, i, make_dirs, _sources=sources)
+        self.saveTextMetadata(root, properties)
+
+    def writeCovMatrix(self, filename=None):
+        """mcsamples.py:637-657, covmat.py:41-49: ``# name1 name2 ...`` of the non-derived parameters, then their covariance
+        as "%15.7E" rows; default ``rootdirname + ".covmat"``.  An n x n matrix: np.savetxt on the host, as the reference."""
+        n = self.paramNames.numNonDerived()
+        with open(filename or self.rootdirname + ".covmat", "wb") as f:
+            f.write(("# " + " ".join(self.paramNames.list()[:n]) + "\n").encode("UTF-8"))
+            np.savetxt(f, self.fullcov[:n, :n], "%15.7E")
+
+    def writeCorrelationMatrix(self, filename=None):
+        """mcsamples.py:659-666: the correlation matrix as "%15.7E" rows (np.savetxt on the host: n x n); default
+        ``rootdirname + ".corr"``"""
+        np.savetxt(filename or self.rootdirname + ".corr", self.getCorrelationMatrix(), fmt="%15.7E")
 
     def getFractionIndices(self, weights, n):
         """mcsamples.py:668-680: row indices splitting the total weight into n equal parts"""

@@ -20,6 +20,7 @@ class ParamInfo(_PlotParamInfo):
             super().__init__(name=name, label=label or name)
         self.name = name
         self.label = label or name
+        self._label_given = bool(label)  # the reference's label of a parameter without one is "" (what string() writes)
         self.isDerived = False
         self.limmin = self.limmax = None
         self.has_limits_bot = self.has_limits_top = self.has_limits = False
@@ -37,6 +38,19 @@ class ParamInfo(_PlotParamInfo):
         """paramnames.py:126-130: what the plotting layer writes on an axis"""
         return "$" + self.label + "$" if self.label else self.name
 
+    def string(self, wantComments=True):
+        """paramnames.py:137-144: the parameter's line of a .paramnames file"""
+        res = self.name
+        if self.isDerived:
+            res += "*"
+        res = res + "\t" + (self.label if getattr(self, "_label_given", True) or self.label != self.name else "")
+        if wantComments and self.comment != "":
+            res = res + "\t#" + self.comment
+        return res
+
+    def __str__(self):
+        return self.string()
+
     def __repr__(self):
         return "ParamInfo(%s)" % self.name
 
@@ -45,6 +59,15 @@ class ParamNames:
     def __init__(self, names, labels=None):
         labels = labels or [None] * len(names)
         self.names = [ParamInfo(n, lab) for n, lab in zip(names, labels)]
+
+    def __str__(self):
+        """paramnames.py:391-395"""
+        return "".join(par.string() + "\n" for par in self.names)
+
+    def saveAsText(self, filename):
+        """paramnames.py:397-404: write the .paramnames file"""
+        with open(filename, "w", encoding="utf-8") as f:
+            f.write(str(self))
 
     def parWithName(self, name, error=False, renames=None):
         """paramnames.py:232-255: the parameter called ``name`` -- by its own name, by one of its ``renames``, or through the

@@ -7,9 +7,31 @@ class ParamBounds:
 
     def __init__(self):
         self.lower, self.upper, self.periodic = {}, {}, set()
+        self.names = []  # in the order the ranges were first set: the order of the lines of a .ranges file
+
+    def __str__(self):
+        """parampriors.py:45-63: one line per parameter, ``%22s%17s%17s`` of name, lower, upper (``%15.7E``, or N for an open
+        side), and ``periodic`` behind a periodic one"""
+        s = ""
+        for name in self.names:
+            lo, hi = self.getLower(name), self.getUpper(name)
+            lim1 = "%15.7E" % lo if lo is not None else "    N"
+            lim2 = "%15.7E" % hi if hi is not None else "    N"
+            if name in self.periodic:
+                s += "%22s%17s%17s%10s\n" % (name, lim1, lim2, "periodic")
+            else:
+                s += "%22s%17s%17s\n" % (name, lim1, lim2)
+        return s
+
+    def saveToFile(self, fileName):
+        """parampriors.py:65-72: write the .ranges file"""
+        with open(fileName, "w", encoding="utf-8") as f:
+            f.write(str(self))
 
     def setRange(self, name, rng):
         lo, hi = rng[0], rng[1]
+        if not (lo is None and hi is None) and name not in self.names:  # parampriors.py:82-83, 98-99
+            self.names.append(name)
         if len(rng) > 2 and rng[2] in (True, "periodic"):
             self.periodic.add(name)
         elif name in self.periodic:
@@ -23,6 +45,8 @@ class ParamBounds:
     def setFixed(self, name, value):
         """parampriors.py:78-79: a fixed parameter is a zero-width range"""
         self.lower[name] = self.upper[name] = float(value)
+        if name not in self.names:
+            self.names.append(name)
 
     def fixedValue(self, name):
         lo, hi = self.lower.get(name), self.upper.get(name)

@@ -507,6 +507,36 @@ int gd_draw_single_rows(gd_ctx* ctx, const uint64_t* pcg_state, const void* d_ra
                         void* d_rows, int64_t capacity, int64_t* count_out);
 int gd_gather_rows(gd_ctx* ctx, const void* d_rows, int64_t K, const int32_t* cols, int32_t m, void* d_out);
 
+/* ---------------------------------------------------------------- chain export: text on the device -------
+ * The text that np.savetxt(fmt="%W.Pe") makes of sample rows (chains.py:1063-1085 saveAsText, mcsamples.py:596-601 the file
+ * branch of makeSingleSamples) or of a matrix, formatted on the device: every value is Python's "%W.Pe" % x byte for
+ * byte (csrc/fmtdouble.hpp: correctly rounded from the exact binary value, ties to even, at least two exponent digits,
+ * "inf" / "-inf" / "nan" without a sign on NaN, upper case for `upper`), right-justified to `width`; with sep = 1 one
+ * space separates the fields of a row (np.savetxt), with sep = 0 nothing does ("%16.7E" rows); every row ends with '\n'.
+ * prec is 0..17, width 0..32; a field takes at most max(width, prec + 8) + 1 bytes, separator or newline included, so
+ * rows * m * that many bytes always fit.
+ * gd_format_rows: field j of a row is srcs[j]: a resident column (spare columns included: gd_set_extra_column is how a
+ *   loglike vector gets there), GD_FMT_SRC_WEIGHT = the sample weights (1.0 when the set is unweighted; the sample weights
+ *   also while auxiliary weights are selected), or the constants GD_FMT_SRC_ZERO = 0.0 / GD_FMT_SRC_ONE = 1.0.  The rows are
+ *   either the contiguous range [row_lo, row_hi) (d_rows NULL) or the K rows of the device int32 list d_rows, in list order
+ *   (row_lo = row_hi = 0); a listed row number outside the sample set formats every field as NaN, as gd_gather_rows does.
+ * gd_format_matrix: the K x m fp64 matrix at d_x (device), element (r, c) at d_x[r * row_stride + c * col_stride].
+ * d_out (device, `capacity` bytes) receives the text and *bytes_out its size.  Nothing is written at or beyond `capacity`:
+ *   when the text is longer the call writes nothing, sets *bytes_out to the size needed and returns GD_FORMAT_MORE_BYTES.
+ * GD_ERR_BADARG, before any launch: no samples uploaded, a column or code out of range, an empty or out-of-range row
+ *   interval, both or neither row selector, prec or width out of range, m < 1, or so many fields that one row of them
+ *   does not fit in LDS (about 900 at the widest format).  A list or matrix with K = 0 gives 0 bytes.
+ * A block owns a tile of rows and transposes through LDS (column-major loads, row-major text); a first pass counts the
+ *   bytes of every tile, one block scans them, a second pass formats again and writes.  Blocks until the text is complete. */
+#define GD_FORMAT_MORE_BYTES (-22)
+#define GD_FMT_SRC_WEIGHT (-1)
+#define GD_FMT_SRC_ZERO (-2)
+#define GD_FMT_SRC_ONE (-3)
+int gd_format_rows(gd_ctx* ctx, const int32_t* srcs, int32_t m, int64_t row_lo, int64_t row_hi, const void* d_rows, int64_t K,
+                   int32_t width, int32_t prec, int32_t upper, int32_t sep, void* d_out, int64_t capacity, int64_t* bytes_out);
+int gd_format_matrix(gd_ctx* ctx, const void* d_x, int64_t K, int32_t m, int64_t row_stride, int64_t col_stride,
+                     int32_t width, int32_t prec, int32_t upper, int32_t sep, void* d_out, int64_t capacity, int64_t* bytes_out);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
