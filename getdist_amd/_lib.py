@@ -155,6 +155,8 @@ SIGNATURES = {
     "gd_gather_rows": (C.c_int, [_p, _p, _i64, _pi32, _i32, _p]),
     "gd_format_rows": (C.c_int, [_p, _pi32, _i32, _i64, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _i64, _pi64]),
     "gd_format_matrix": (C.c_int, [_p, _p, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _p, _i64, _pi64]),
+    "gd_parse_scan": (C.c_int, [_p, _p, _i64, _i32, _pi64, _pi32, _pi64]),
+    "gd_parse_rows": (C.c_int, [_p, _p, _i64, _i32, _i64, _i32, _p, _i64, _i64, _p, _i64, _pi64]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
@@ -164,11 +166,30 @@ GD_DRAW_MORE_ROWS = -21
 GD_FORMAT_MORE_BYTES = -22
 GD_FMT_SRC_WEIGHT, GD_FMT_SRC_ZERO, GD_FMT_SRC_ONE = -1, -2, -3
 GD_FMT_MAX_PREC, GD_FMT_MAX_WIDTH = 17, 32
+GD_PARSE_NOT_PLAIN = -23
+GD_PARSE_MAX_LINE = 8192
 
 
 def format_field_bytes(width, prec):
     """Upper bound of one formatted field, separator or newline included (gd_format_rows / gd_format_matrix)."""
     return max(int(width), int(prec) + 8) + 1
+
+
+def skipped_text_bytes(f, skiprows):
+    """Bytes that the first ``skiprows`` lines of the binary file ``f`` take, read off ``f``; None when only a text-mode
+    reader can tell.  np.loadtxt and pandas skip lines of a file opened as text, where a lone '\\r' ends a line as well and
+    the bytes must decode; the device never sees the skipped bytes, so a '\\r' that is not directly followed by '\\n', a
+    NUL or a byte >= 0x80 among them is left to the host parser (Context.parse_text declines)."""
+    start = 0
+    for _ in range(int(skiprows or 0)):
+        line = f.readline()  # up to and including the next '\n'
+        if not line:
+            break
+        if b"\r" in line.replace(b"\r\n", b"") or b"\0" in line or not line.isascii():
+            return None
+        start += len(line)
+    return start
+
 
 _lib = None
 
@@ -944,6 +965,166 @@ class Context:
         stream (ordered after the compute stream's work so far); copy_mark() / copy_wait() tell when it has landed."""
         if nbytes:
             self._check(self.lib.gd_memcpy_d2h_async(self.h, host.ctypes.data, buf.ptr, int(nbytes)))
+
+    # ---- chain ingestion
+    PARSE_CHUNK_BYTES = 64 << 20  # text per read / copy / scan step of parse_text: two page-locked blocks of this size
+    PARSE_MEMORY_SHARE = 0.5      # parse_text declines a text that, with its output, exceeds this share of the free HBM
+    PARSE_FIX_CAPACITY = 1 << 16  # undecided tokens listed per parse_rows call; more makes parse_text decline
+
+    def parse_scan(self, text, nbytes, last=True, offset=0):
+        """gd_parse_scan of ``nbytes`` bytes of the device buffer ``text`` from ``offset`` on: (status, data rows, fields per
+        row, bytes consumed) with status GD_OK or GD_PARSE_NOT_PLAIN; any other error raises."""
+        rows, m, used = C.c_int64(), C.c_int32(), C.c_int64()
+        rc = self.lib.gd_parse_scan(self.h, (text.ptr + int(offset)) if text is not None else None, int(nbytes), int(bool(last)),
+                                    C.byref(rows), C.byref(m), C.byref(used))
+        if rc != GD_PARSE_NOT_PLAIN:
+            self._check(rc)
+        return rc, rows.value, m.value, used.value
+
+    def parse_rows(self, text, nbytes, rows, m, out, ld, row_offset=0, last=True, fix_capacity=None, offset=0):
+        """gd_parse_rows: field j of data row r of the text goes to element j * ld + row_offset + r of the fp64 device
+        buffer ``out``.  Returns (status, fixes, fix count): ``fixes`` is the (k, 4) int64 array of the listed undecided
+        tokens -- (row in ``out``, field, byte offset from ``offset``, length) -- and k < fix count when the list was
+        short.  ``out`` must hold at least m * ld values (checked here: the library sees only a pointer)."""
+        cap = self.PARSE_FIX_CAPACITY if fix_capacity is None else int(fix_capacity)
+        if out is not None and int(m) * int(ld) * 8 > out.nbytes:
+            raise ValueError("the output buffer holds %d bytes, m * ld values take %d" % (out.nbytes, int(m) * int(ld) * 8))
+        fix = self.alloc(cap * 32) if cap > 0 else None
+        n = C.c_int64()
+        try:
+            rc = self.lib.gd_parse_rows(self.h, (text.ptr + int(offset)) if text is not None else None, int(nbytes), int(bool(last)),
+                                        int(rows), int(m), out.ptr if out is not None else None, int(ld), int(row_offset),
+                                        fix.ptr if fix is not None else None, cap, C.byref(n))
+            if rc != GD_PARSE_NOT_PLAIN:
+                self._check(rc)
+            k = min(n.value, cap) if rc == 0 else 0
+            fixes = fix.to_host((k, 4), dtype=np.int64) if k else np.zeros((0, 4), dtype=np.int64)
+        finally:
+            if fix is not None:
+                fix.free()
+        return rc, fixes, n.value
+
+    def parse_text(self, source, skiprows=0, chunk_bytes=None, alloc=None):
+        """
+        np.loadtxt of a whole text on the device.  ``source`` is a path or a bytes-like object; ``skiprows`` line ends are
+        passed over on the host first.  The text is read in chunks of ``chunk_bytes`` into two page-locked blocks by a
+        helper thread and copied into ONE device buffer that holds the whole text; the read of chunk k + 1 overlaps the
+        copy and the gd_parse_scan of chunk k.  Every scan starts behind the last line end the previous one consumed, so a
+        line that straddles a chunk boundary is scanned once it is whole.  With the row and field counts known the
+        m x N output is allocated, gd_parse_rows runs once per scanned piece, and the block is fetched once into
+        page-locked memory (``alloc``, default pinned_block).
+
+        Returns None when the device route declines -- a text that is not plain (GD_PARSE_NOT_PLAIN), skipped lines that
+        only a text-mode reader can count (skipped_text_bytes), no rows, a short fix list, text plus output above
+        PARSE_MEMORY_SHARE of the free device memory, or an allocation that fails (GD_ERR_NOMEM) -- and otherwise
+        dict(array=(N, m) column-major view, fixes=[(row, field, byte offset in the source, length), ...]): the listed
+        tokens hold NaN and are the caller's to convert (chainfiles.loadNumpyTxt uses float()).
+        """
+        import io
+        import threading
+        import queue
+
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            f = io.BytesIO(bytes(source))
+            size = len(source)
+        else:
+            f = open(os.fspath(source), "rb")
+            size = os.path.getsize(os.fspath(source))
+        text = out = None
+        reader = None
+        stop = []
+        try:
+            start = skipped_text_bytes(f, skiprows)
+            if start is None:
+                return None
+            total = size - start
+            if total <= 0:
+                return None
+            free_hbm = self.device_info()["hbm_free"]
+            if total > self.PARSE_MEMORY_SHARE * free_hbm:
+                return None
+            chunk = max(int(chunk_bytes or self.PARSE_CHUNK_BYTES), 1)
+            chunk = min(chunk, total)
+            text = self.alloc(total)
+            host = [self.pinned_array((chunk,), np.uint8) for _ in range(2 if total > chunk else 1)]
+            free, todo = queue.Queue(), queue.Queue()
+            for b in range(len(host)):
+                free.put(b)
+
+            def read_chunks():  # fills the page-locked blocks in turn; the caller's thread copies and scans them
+                try:
+                    done = 0
+                    while done < total and not stop:
+                        b = free.get()
+                        if b is None:
+                            return
+                        want = min(chunk, total - done)
+                        got = f.readinto(memoryview(host[b])[:want])
+                        if got != want:
+                            raise OSError("short read: the file changed while it was being parsed")
+                        done += got
+                        todo.put((b, got))
+                    todo.put(None)
+                except BaseException as e:  # noqa: BLE001 -- handed to the caller's thread
+                    todo.put(e)
+
+            reader = threading.Thread(target=read_chunks, name="getdist_amd-text-reader")
+            reader.start()
+            pieces, m, N = [], 0, 0  # (offset, bytes, rows, last) of every scanned piece
+            have = scanned = 0
+            while True:
+                item = todo.get()
+                if isinstance(item, BaseException):
+                    raise item
+                if item is not None:
+                    b, got = item
+                    self._check(self.lib.gd_memcpy_h2d(self.h, text.ptr + have, host[b].ctypes.data, got))
+                    free.put(b)
+                    have += got
+                last = have == total
+                rc, rows, fields, used = self.parse_scan(text, have - scanned, last=last, offset=scanned)
+                if rc != 0:
+                    return None
+                if rows:
+                    if m and fields != m:
+                        return None
+                    m = fields
+                if used:
+                    pieces.append((scanned, used, rows, last))
+                    scanned += used
+                    N += rows
+                if last:
+                    break
+            if N == 0:
+                return None
+            if total + 8 * m * N > self.PARSE_MEMORY_SHARE * free_hbm:
+                return None
+            out = self.alloc(8 * m * N)
+            fixes, row0 = [], 0
+            for off, nb, rows, last in pieces:
+                if rows:
+                    rc, fx, count = self.parse_rows(text, nb, rows, m, out, N, row_offset=row0, last=last, offset=off)
+                    if rc != 0 or count > len(fx):
+                        return None
+                    fixes += [(int(r), int(j), int(o) + off + start, int(ln)) for r, j, o, ln in fx]
+                row0 += rows
+            flat = (alloc or self.pinned_block)((m * N,), np.float64)
+            self._check(self.lib.gd_memcpy_d2h(self.h, flat.ctypes.data, out.ptr, flat.nbytes))
+            return dict(array=flat.reshape((m, N)).T, fixes=fixes)
+        except GdhipError as e:
+            if e.code != GD_ERR_NOMEM:
+                raise
+            return None  # the share of free memory was there, a block of it was not: the host route needs none
+        finally:
+            stop.append(True)
+            if reader is not None:
+                free.put(None)
+                free.put(None)
+                reader.join()
+            f.close()
+            for d in (text, out):
+                if d is not None:
+                    d.free()
 
     # ---- mean likelihoods
     def like_weights(self, loglikes, mode, mean_loglike):

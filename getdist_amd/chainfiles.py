@@ -4,8 +4,11 @@ Chain ingestion: GetDist's plain-text chain format -- ``ro
 per line, ``*`` = derived) and ``root.ranges`` (``name  lower  upper``, ``N`` = unbounded) -- read into a getdist_amd
 MCSamples.  Follows chains.py:77-125 (file matching, loadNumpyTxt), chains.py:228-246 / mcsamples.py:501-528
 (ignore_rows burn-in per chain, fixed-parameter deletion, makeSingle) and paramnames.py / parampriors.py for the two
-side files.  The parse itself is host work (pandas' C tokenizer when present: ~10x np.loadtxt); the columns go to the
-device in the same SoA layout as array input.
+side files.  With a device context the parse itself runs on the device (``Context.parse_text``: gd_parse_scan /
+gd_parse_rows, every value bit-equal to np.loadtxt); without one, or for a text the device declines, it is host work:
+pandas' C tokenizer with ``float_precision="round_trip"`` when present, else np.loadtxt.  (Measured with numpy 2.2.6 on a
+161 MB file, 200 000 x 52 at ``%.8e``: np.loadtxt 1.83 s = 88 MB/s, pandas round_trip 5.18 s = 31 MB/s -- pandas is no
+longer the faster of the two.)  The columns go to the device in the same SoA layout as array input.
 
 Chain export is the way back: ``write_text_rows`` streams rows of the resident sample set into a text file whose bytes are
 np.savetxt's, formatted on the device (gd_format_rows) in chunks that overlap the file writes.
@@ -35,10 +38,48 @@ def chainFiles(root, chain_indices=None, ext=".txt", separator="_", first_chain=
     return files
 
 
-def loadNumpyTxt(fname, skiprows=None):
-    """chains.py:115-125: a 2D float array from a whitespace-separated text file (``#`` comments allowed)."""
+def patch_fixes(arr, fixes, read_token):
+    """Resolves the tokens the device left undecided: ``fixes`` lists (row, field, byte offset, length), ``read_token(offset,
+    length)`` returns the token's bytes, and float() -- which agrees with np.loadtxt inside the grammar the device accepts --
+    gives the double that goes into ``arr[row, field]``."""
+    for row, field, offset, length in fixes:
+        arr[row, field] = float(bytes(read_token(offset, length)).decode("ascii"))
+    return arr
+
+
+def _load_text_device(fname, skiprows, parse_text, parse_args):
+    """The device route of loadNumpyTxt: the (N, m) array, or None when the device declines the file."""
+    res = parse_text(fname, skiprows=skiprows or 0, **parse_args)
+    if res is None or res["array"].shape[1] < 3:
+        return None  # np.atleast_2d(np.loadtxt) of a one-column file has a shape of its own, and read_root discards such files
+    arr = res["array"]
+    if len(res["fixes"]):
+        with open(fname, "rb") as f:
+            def read_token(offset, length):
+                f.seek(offset)
+                return f.read(length)
+
+            patch_fixes(arr, res["fixes"], read_token)
+    return arr
+
+
+def loadNumpyTxt(fname, skiprows=None, ctx=None, _parse_args=None):
+    """chains.py:115-125: a 2D float array from a whitespace-separated text file (``#`` comments allowed).
+
+    With a context that can parse (``ctx.parse_text``: the device context, not the numpy test double) the text is copied to
+    the device in chunks and parsed there, bit-equal to np.loadtxt; the few tokens the device cannot decide come back as
+    a list and are converted here.  Whatever the device declines -- a ragged or otherwise not plain text, skipped lines
+    that hold a lone CR or bytes outside ASCII (only a text-mode reader counts and decodes them as the reference does),
+    fewer than 3 columns, a short fix list, a file too large for the free device memory -- takes the host route below for the whole
+    file, so the values and the ValueError of a half-written file are the reference parser's own.  ``_parse_args`` are
+    keyword arguments for parse_text (tests cut the file into small chunks with it)."""
     if os.path.getsize(fname) == 0:
         return np.zeros((0, 0))
+    parse_text = getattr(ctx, "parse_text", None)
+    if parse_text is not None:
+        arr = _load_text_device(fname, skiprows, parse_text, _parse_args or {})
+        if arr is not None:
+            return arr
     try:
         import pandas as pd
 
@@ -317,12 +358,12 @@ def read_soa_cache(path, alloc=None):
     return flat.reshape((ncol, N)).T, head["rows"]
 
 
-def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None):
+def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None, ctx=None):
     """
     Everything ``MCSamples(root=...)`` / ``loadMCSamples`` read from disk (mcsamples.py:47-146, chains.py:1368-1405):
     the chain files (or the binary cache when it is newer than all of them), ``.paramnames`` and ``.ranges``.
     Returns dict(samples=[per-chain (rows, n)], weights=[...], loglikes=[...], names, labels, derived, ranges,
-    from_cache).  No burn-in is removed here.
+    from_cache).  No burn-in is removed here.  ``ctx`` parses the chain files on the device (loadNumpyTxt).
     """
     from .chains import WeightedSampleError
 
@@ -345,7 +386,7 @@ def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None):
     if chains is None:
         chains = []
         for fname in files:
-            cols = loadNumpyTxt(fname)
+            cols = loadNumpyTxt(fname, ctx=ctx)
             if cols.shape[0] == 0 or cols.shape[1] < 3:
                 continue  # "Ignored file (likely empty)" (chains.py:1400-1403)
             chains.append(cols)

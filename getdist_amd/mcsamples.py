@@ -286,7 +286,7 @@ class MCSamples(Chains):
 
             self.ctx = (_context_factory or Context)(device)  # page-locked landing buffer for the binary cache
             loaded = chainfiles.read_root(root, chain_exclude, no_cache,
-                                          alloc=getattr(self.ctx, "pinned_block", None))
+                                          alloc=getattr(self.ctx, "pinned_block", None), ctx=self.ctx)
             samples, weights, loglikes = loaded["samples"], loaded["weights"], loaded["loglikes"]
             names = names or loaded["names"]
             labels = labels or loaded["labels"]

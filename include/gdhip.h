@@ -537,6 +537,40 @@ int gd_format_rows(gd_ctx* ctx, const int32_t* srcs, int32_t m, int64_t row_lo, 
 int gd_format_matrix(gd_ctx* ctx, const void* d_x, int64_t K, int32_t m, int64_t row_stride, int64_t col_stride,
                      int32_t width, int32_t prec, int32_t upper, int32_t sep, void* d_out, int64_t capacity, int64_t* bytes_out);
 
+/* ---------------------------------------------------------------- chain ingestion: text parsed on the device -------
+ * The doubles that np.loadtxt (chains.py:115-125 loadNumpyTxt) makes of whitespace-separated decimal text, parsed from a
+ * block of text resident on the device: every value is correctly rounded (ties to even; overflow gives +-inf, underflow
+ * +-0, "-0" keeps its sign, "nan" / "inf" / "infinity" in any letter case) by integer arithmetic only (csrc/parsedouble.hpp).
+ * Separators are space, '\t', '\v', '\f' and a '\r' directly before '\n'; '#' opens a comment that runs to the end of the
+ * line; a line without a token is skipped.  A text is NOT PLAIN, and both calls then return GD_PARSE_NOT_PLAIN with
+ * nothing written, when rows differ in their number of fields, a '\r' is not followed by '\n', a byte is NUL or >= 0x80,
+ * a token is outside np.loadtxt's grammar for a float field ("1_0", hex, "1d5", "1e", ...) or a line is longer than
+ * GD_PARSE_MAX_LINE bytes, its '\n' included (a block stages the lines it owns through LDS): the caller then parses the file
+ * on the host.
+ * gd_parse_scan: scans d_text[0, nbytes) from its start up to its last '\n'; with last != 0 the text ends the file and a
+ *   final line without '\n' is included.  *rows_out = data rows, *fields_out = fields per row (0 when there is no row),
+ *   *consumed_out = bytes consumed (nbytes with `last`; otherwise the offset behind the last '\n', from where the caller
+ *   continues once more text has arrived; 0 when there is no '\n').
+ * gd_parse_rows: parses the same block again -- nbytes is what the scan consumed, rows and m what it reported -- and stores
+ *   field j of data row r at d_out[j * ld + row_offset + r] (fp64, the column-major layout of the context and of the
+ *   binary cache).  A token the 128-bit fast path cannot decide (about one in 2^73 of random text, but every exact tie
+ *   scaled by a negative power of ten, a token of more than 19 digits at or next to a tie -- where its first 19 digits and
+ *   their successor round apart, about one long token in a thousand -- and whatever lies outside 1e-310 .. 1e345) is
+ *   stored as NaN and listed: entry k of d_fix (device, fix_capacity entries of four int64) = {row_offset + r, j, byte
+ *   offset of the token in d_text, its length}, in no particular order.  *fix_count_out counts them all, also beyond
+ *   fix_capacity -- the list is then short and the caller knows.  The call scans first, so a text that is not plain leaves
+ *   d_out untouched.
+ * GD_ERR_BADARG before any launch: null pointers, negative sizes, ld < row_offset + rows; after the scan: rows, m or nbytes
+ *   that are not what the scan of this block reports.  Neither call needs an uploaded sample set.  nbytes = 0 does nothing.
+ * Tiles of 24 KiB of text; a first pass counts the rows of every tile, one block scans the counts, a second pass parses
+ *   and stores with lanes running along rows.  Both calls block until their results are complete. */
+#define GD_PARSE_NOT_PLAIN (-23)
+#define GD_PARSE_MAX_LINE 8192
+int gd_parse_scan(gd_ctx* ctx, const void* d_text, int64_t nbytes, int32_t last, int64_t* rows_out, int32_t* fields_out,
+                  int64_t* consumed_out);
+int gd_parse_rows(gd_ctx* ctx, const void* d_text, int64_t nbytes, int32_t last, int64_t rows, int32_t m, void* d_out, int64_t ld,
+                  int64_t row_offset, void* d_fix, int64_t fix_capacity, int64_t* fix_count_out);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
