@@ -109,6 +109,7 @@ SIGNATURES = {
     "gd_density2d_enqueue": (C.c_int, [_p, _i32, _i32, _p, _pd, _pd, _pd, _pi32, _pi32, _i32, _i32, _p, _p]),
     "gd_density2d_enqueue_indexed": (C.c_int, [_p, _i32, _i32, _p, _pi32, _pd, _pd, _pd, _pi32, _pi32, _i32, _i32, _p, _p]),
     "gd_attach_samples": (C.c_int, [_p, _p]),
+    "gd_clone_samples": (C.c_int, [_p, _p]),
     "gd_bind_thread": (C.c_int, [_p]),
     "gd_contour_levels": (C.c_int, [_p, _i32, _i32, _p, _pd, _i32, _pd, _pi32]),
     "gd_limits1d": (C.c_int, [_p, _i32, _i32, _pd, _pd, _pd, _pd, _i32, _i32, _pd, _pi32]),
@@ -515,6 +516,12 @@ class Context:
         """Borrow ``owner``'s resident sample set (same device, no copy): this context becomes a second lane."""
         self._check(self.lib.gd_attach_samples(self.h, owner.h))
         self.N, self.n, self.weighted = owner.N, owner.n, owner.weighted
+
+    def clone_samples(self, src):
+        """A resident sample set of this context's OWN with the columns and weights of ``src``'s (same device), copied
+        device to device; ``src`` may be re-uploaded or closed afterwards."""
+        self._check(self.lib.gd_clone_samples(self.h, src.h))
+        self.N, self.n, self.weighted = src.N, src.n, src.weighted
 
     def bind_thread(self):
         self._check(self.lib.gd_bind_thread(self.h))

@@ -52,6 +52,25 @@ def covToCorr(cov, copy=True):
     return cov
 
 
+def getSignalToNoise(C, noise=None, R=None, eigs_only=False):
+    """chains.py:131-153: eigenvalues w (ascending; small = well constrained against the noise) of M = R C R^T, where R
+    defaults to the inverse Cholesky root of ``noise``, and unless ``eigs_only`` also the matrix whose rows are the
+    eigenvectors of M mapped back through R."""
+    if R is None:
+        if noise is None:
+            raise WeightedSampleError("Must give noise or rotation R")
+        R = np.linalg.inv(np.linalg.cholesky(noise))
+    M = np.dot(R, C).dot(R.T)
+    if eigs_only:
+        return np.linalg.eigvalsh(M)
+    w, U = np.linalg.eigh(M)
+    return w, np.dot(U.T, R)
+
+
+class ParSamples:
+    """chains.py:172-175: the attribute bag of getParams / setParams (one sample vector per parameter name)"""
+
+
 class ParamConfidenceData:
     """Handle returned by initParamConfidenceData (chains.py:176-178 namedtuple in the reference)."""
 
@@ -406,6 +425,10 @@ class WeightedSamples:
 
     def corr(self, pars=None):
         return covToCorr(self.cov(pars))
+
+    def getSignalToNoise(self, params, noise=None, R=None, eigs_only=False):
+        """chains.py:840-851: getSignalToNoise of the covariance of ``params`` (one device pass; the rest is m x m host algebra)"""
+        return getSignalToNoise(self.cov(params), noise, R, eigs_only)
 
     def getCorrelationMatrix(self):
         if self.correlationMatrix is None:
@@ -893,16 +916,42 @@ class Chains(WeightedSamples):
     def getRenames(self):
         return self.paramNames.getRenames()
 
+    def updateRenames(self, renames):
+        """chains.py:1258-1262"""
+        self.paramNames.updateRenames(renames)
+
+    def setParams(self, obj):
+        """chains.py:1264-1289: give ``obj`` one attribute per parameter name holding its sample vector.  A dotted name
+        aa.bb.cc becomes obj.aa.bb.cc through ParSamples sub-objects; a parameter aa whose name is also the head of a dotted
+        one is reached as obj.aa.value.  Returns ``obj``."""
+        holders = []
+        for par in self.paramNames.names:  # every sub-object first: whether a name holds one does not depend on the order
+            *heads, leaf = par.name.split(".")
+            holder = obj
+            for head in heads:
+                if not hasattr(holder, head):
+                    setattr(holder, head, ParSamples())
+                holder = getattr(holder, head)
+            holders.append((holder, leaf))
+        for j, (holder, leaf) in enumerate(holders):
+            if isinstance(getattr(holder, leaf, None), ParSamples):
+                getattr(holder, leaf).value = self.samples[:, j]
+            else:
+                setattr(holder, leaf, self.samples[:, j])
+        return obj
+
     def getParams(self):
-        """chains.py:1252-1268 in spirit: an object with one attribute per parameter name holding its sample vector"""
+        """chains.py:1291-1301: a ParSamples with one attribute per parameter name holding its sample vector"""
+        return self.setParams(ParSamples())
 
-        class ParSamples:
-            pass
-
-        out = ParSamples()
+    def getParamSampleDict(self, ix, want_derived=True):
+        """chains.py:1303-1317: {"weight", "loglike", parameter name: value} of sample row ``ix`` (the weight of a unit-weight
+        set is 1.0; without loglikes this raises TypeError, as indexing None does in the reference)"""
+        res = {"weight": 1.0 if self.weights is None else self.weights[ix], "loglike": self.loglikes[ix]}
         for j, par in enumerate(self.paramNames.names):
-            setattr(out, par.name, self.samples[:, j])
-        return out
+            if want_derived or not par.isDerived:
+                res[par.name] = self.samples[ix, j]
+        return res
 
     # ---- base statistics (chains.py:1340-1352) ---------------------------------------------------------------
     def _partial_moments(self, lo, hi):

@@ -603,8 +603,35 @@ int gd_upload_shard(gd_ctx* ctx, const double* X_cols, int64_t N, int64_t n, int
     return upload_common(ctx, X_cols, N, n, 1, col_stride, weights, col_first, col_count);
 }
 
+// The two ends every way of giving a context a sample set of its own goes through (gd_upload, gd_upload_shard,
+// gd_clone_samples): upload_release leaves the context EMPTY (the old set, its index columns, prefix sums, bucket columns
+// and auxiliary weights are gone), upload_install hands it the finished allocations.
+static int upload_release(gd_ctx* ctx);
+static void upload_install(gd_ctx* ctx, double* cols, double* w, unsigned char* w8, bool integral, double wsum, int64_t N,
+                           int64_t n, int64_t ld);
+
 static int upload_common(gd_ctx* ctx, const double* X, int64_t N, int64_t n, int64_t row_stride, int64_t col_stride,
                          const double* weights, int64_t shard_first, int64_t shard_count) {
+    GD_TRY(upload_release(ctx));
+    const int64_t ld = (N + 511) / 512 * 512;
+    double *cols = nullptr, *w = nullptr;
+    unsigned char* w8 = nullptr;
+    bool integral = false;
+    double wsum = 0;
+    const int rc = upload_build(ctx, X, N, n, row_stride, col_stride, weights, ld, &cols, &w, &w8, &integral, &wsum, shard_first,
+                                shard_count);
+    if (rc != GD_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (cols) (void)hipFree(cols);
+        if (w) (void)hipFree(w);
+        if (w8) (void)hipFree(w8);
+        return rc;
+    }
+    upload_install(ctx, cols, w, w8, integral, wsum, N, n, ld);
+    return GD_OK;
+}
+
+static int upload_release(gd_ctx* ctx) {
     GD_HIP(hipSetDevice(ctx->device));
     GD_TRY(gd_stream_sync(ctx));
     // The stream of a context that OWNS a sample set is urgent: in a batched call it carries the optimiser's stage A, whose
@@ -633,20 +660,11 @@ static int upload_common(gd_ctx* ctx, const double* X, int64_t N, int64_t n, int
     ctx->w_sum = ctx->w_main_sum = 0;
     ctx->N = ctx->n = ctx->ld = 0;
     ctx->bq.reset();
-    const int64_t ld = (N + 511) / 512 * 512;
-    double *cols = nullptr, *w = nullptr;
-    unsigned char* w8 = nullptr;
-    bool integral = false;
-    double wsum = 0;
-    const int rc = upload_build(ctx, X, N, n, row_stride, col_stride, weights, ld, &cols, &w, &w8, &integral, &wsum, shard_first,
-                                shard_count);
-    if (rc != GD_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (cols) (void)hipFree(cols);
-        if (w) (void)hipFree(w);
-        if (w8) (void)hipFree(w8);
-        return rc;
-    }
+    return GD_OK;
+}
+
+static void upload_install(gd_ctx* ctx, double* cols, double* w, unsigned char* w8, bool integral, double wsum, int64_t N,
+                           int64_t n, int64_t ld) {
     ctx->cols = cols;
     ctx->w = w;
     ctx->w8 = w8;
@@ -656,6 +674,56 @@ static int upload_common(gd_ctx* ctx, const double* X, int64_t N, int64_t n, int
     ctx->n = n;
     ctx->ld = ld;
     ctx->bq = std::make_shared<BucketCols>();  // (the old set's bucket columns go with its last user)
+}
+
+// Device-to-device: dst's own allocations, filled on dst's stream behind everything src's stream has been given so far.
+// What the upload derives from the weights (integral flag, byte multiplicities, their total) is a function of the weights
+// alone, so it is taken over instead of being computed again.  While src has auxiliary weights selected its SAMPLE
+// weights are the parked ones.
+static int clone_build(gd_ctx* ctx, gd_ctx* src, double** cols_out, double** w_out, unsigned char** w8_out) {
+    const int64_t n = src->n, ld = src->ld;
+    const double* sw = src->w_sel ? src->w_main : src->w;
+    const unsigned char* sw8 = src->w_sel ? src->w8_main : src->w8;
+    hipEvent_t ev = nullptr;
+    GD_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, src->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ev, 0);
+    (void)hipEventDestroy(ev);  // (released once the wait that refers to it has completed)
+    GD_HIP(e);
+    GD_HIP(hipMalloc((void**)cols_out, (size_t)(ld * (n + GD_EXTRA_COLS) * 8)));
+    GD_HIP(hipMemsetAsync(*cols_out + ld * n, 0, (size_t)(ld * GD_EXTRA_COLS * 8), ctx->stream));
+    GD_HIP(hipMemcpyAsync(*cols_out, src->cols, (size_t)(ld * n * 8), hipMemcpyDeviceToDevice, ctx->stream));
+    if (sw) {
+        GD_HIP(hipMalloc((void**)w_out, (size_t)(ld * 8)));
+        GD_HIP(hipMemcpyAsync(*w_out, sw, (size_t)(ld * 8), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (sw8) {
+        GD_HIP(hipMalloc((void**)w8_out, (size_t)ld));
+        GD_HIP(hipMemcpyAsync(*w8_out, sw8, (size_t)ld, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    GD_TRY(gd_stream_sync(ctx));
+    return GD_OK;
+}
+
+int gd_clone_samples(gd_ctx* ctx, gd_ctx* src) {
+    GD_REQUIRE(ctx && src && ctx != src, "bad argument");
+    GD_REQUIRE(src->cols, "the source has no resident sample set");
+    GD_REQUIRE(ctx->device == src->device, "contexts must live on the same device");
+    GD_REQUIRE(src->cols != ctx->cols || ctx->borrowed, "the source borrows the destination's sample set");
+    GD_TRY(upload_release(ctx));
+    double *cols = nullptr, *w = nullptr;
+    unsigned char* w8 = nullptr;
+    const int rc = clone_build(ctx, src, &cols, &w, &w8);
+    if (rc != GD_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (cols) (void)hipFree(cols);
+        if (w) (void)hipFree(w);
+        if (w8) (void)hipFree(w8);
+        return rc;
+    }
+    const bool sel = src->w_sel != 0;
+    upload_install(ctx, cols, w, w8, sel ? src->w_main_integral : src->w_integral, sel ? src->w_main_sum : src->w_sum, src->N,
+                   src->n, src->ld);
     return GD_OK;
 }
 

@@ -176,7 +176,8 @@ class MixtureND:
         float64 vector with one entry per row.  ``params`` (names or column indices, default: this mixture's names looked
         up in the sample set) selects the ``dim`` columns.  Not in the reference, which offers ``-log(mix.pdf(rows))``
         on host rows only; here nothing of size N x dim is formed and the result stays finite far out in the tails.
-        Intended use: ``samples.reweightAddingLogLikes(prior.logLikes(samples))``.
+        Intended use: ``samples.reweightAddingLogLikes(prior.logLikes(samples))`` -- on ``samples.copy()`` to keep the
+        original set as well.
         """
         from .chains import MCSamplesError
 

@@ -15,6 +15,7 @@ compute many densities in batched kernel launches; the per-name/per-pair methods
 them.  There is no CPU fallback: without the library or a GPU, construction raises.
 """
 
+import copy as _copy
 import logging
 import os
 import time
@@ -260,6 +261,7 @@ class MCSamples(Chains):
         self.no_warning_chi2_params = True
         self.chain_offsets = None
         self.chains = None
+        self.indep_thin = 0  # mcsamples.py:245: set by getCorrLengths / getConvergeTests
         self.ctx = None
         for k, v in DEFAULT_SETTINGS.items():
             setattr(self, k, v)
@@ -297,8 +299,11 @@ class MCSamples(Chains):
         ignore_lines = int(self.ignore_rows)
         if samples is None:
             raise MCSamplesError("samples are required")
-        for nm, rng in (ranges or {}).items():
-            self.ranges.setRange(nm, rng)
+        if isinstance(ranges, ParamBounds):  # mcsamples.py:342-343: taken over as a copy
+            self.ranges = _copy.deepcopy(ranges)
+        else:
+            for nm, rng in (ranges or {}).items():
+                self.ranges.setRange(nm, rng)
         samples, weights, loglikes, fixed = self._read_chains(samples, weights, loglikes, ignore_lines)
         self.samples = samples
         self.loglikes = loglikes
@@ -463,6 +468,7 @@ class MCSamples(Chains):
         self._drop_second_lane()
         self._chain_stats_cache = {}
         self._loglikes_col = None  # (an extra-column slot of the old sample set)
+        self.indep_thin = 0  # (a correlation length of the old sample set)
         w = self.weights
         if (filter_weights and self.chain_offsets is None and w is not None and self.min_weight_ratio is not None
                 and self.min_weight_ratio >= 0):
@@ -502,6 +508,151 @@ class MCSamples(Chains):
     def getLower(self, name):
         par = self.paramNames.parWithName(name)
         return getattr(par, "limmin", None) if par else None
+
+    # ---- copies and combined sample sets (mcsamples.py:308-322, 2620-2660) ---------------------------------------
+    # what belongs to this object's contexts, threads and ranks: a copy starts without it (the values it starts with instead;
+    # the two caches of device results get dicts of their own)
+    _NOT_COPIED = dict(ctx=None, _twin=None, _helper_exec=None, _lane_exec=None, _lag_prefetch=None, _pending_results=None,
+                       _parked=None, _neff_share=None, _loglikes_col=None, _like_mode=None, _lane=0, _nlanes=1,
+                       _idx_cols=None, _chain_stats_cache=None)
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy(samples): host state equal-valued and independent; the resident sample set duplicated device to
+        device into a context of the copy's own (gd_clone_samples) -- the columns do not cross PCIe a second time."""
+        if getattr(self, "_column_share", None) is not None:
+            raise MCSamplesError("copy needs every column resident on one device: this context holds only its rank's "
+                                 "share of the columns (copies of a multi-GPU sample set are not supported)")
+        self._finish_pending()
+        new = object.__new__(type(self))
+        memo[id(self)] = new
+        for k, v in list(self.__dict__.items()):
+            if k not in self._NOT_COPIED:
+                new.__dict__[k] = _copy.deepcopy(v, memo)
+        new.__dict__.update(self._NOT_COPIED)
+        new._idx_cols, new._chain_stats_cache = {}, {}
+        new.ctx = self._context_factory(self._device)
+        if hasattr(new.ctx, "clone_samples"):
+            new.ctx.clone_samples(self.ctx)
+        else:  # (a context double of the CPU tests)
+            new.ctx.upload(new.samples, new.weights)
+        return new
+
+    def copy(self, label=None, settings=None):
+        """mcsamples.py:308-322: an independent copy, optionally with another label and / or modified settings"""
+        new = _copy.deepcopy(self)
+        if label:
+            new.label = label
+        if settings is not None:
+            new.needs_update = True
+            new.updateSettings(settings)
+        return new
+
+    def _current_settings(self):
+        """The settings in force, as a dict the constructor / updateSettings takes (an independent copy)."""
+        out = {k: getattr(self, k) for k in DEFAULT_SETTINGS}
+        out.update(no_warning_params=self.no_warning_params, no_warning_chi2_params=self.no_warning_chi2_params)
+        if hasattr(self, "force_twotail"):
+            out["force_twotail"] = self.force_twotail
+        for i, v in getattr(self, "_max_frac_overrides", {}).items():
+            out["max_frac_twotail%d" % (i + 1)] = v
+        return _copy.deepcopy(out)
+
+    def getCombinedSamplesWithSamples(self, samps2, sample_weights=(1, 1)):
+        """
+        mcsamples.py:2620-2660: a new MCSamples of this set's rows followed by ``samps2``'s, over the parameters of
+        ``samps2`` that this set has too (``samps2``'s order, labels and derived flags).  By default the two sets carry the
+        same total weight, times ``sample_weights``; ``sample_weights=None`` appends the weights as they are.  The new
+        object goes through the constructor (ranges and settings of this set, nothing ignored), which uploads it.
+        """
+        mine = self.paramNames.list()
+        pars = [p for p in samps2.paramNames.names if p.name in mine]
+        loglikes = None
+        if self.loglikes is not None and samps2.loglikes is not None:
+            loglikes = np.concatenate([self.loglikes, samps2.loglikes])
+        w1, w2 = self._host_weights(), samps2._host_weights()
+        if sample_weights is None:
+            fac, sample_weights = 1, (1, 1)
+        else:
+            fac = np.sum(w1) / np.sum(w2)
+        weights = np.concatenate([w1 * sample_weights[0], w2 * sample_weights[1] * fac])
+        samples = np.empty((self.numrows + samps2.numrows, len(pars)), order="F")  # the device layout: no transpose
+        for k, p in enumerate(pars):
+            samples[:self.numrows, k] = self.samples[:, self.index[p.name]]
+            samples[self.numrows:, k] = samps2.samples[:, samps2.index[p.name]]
+        new = MCSamples(samples=samples, weights=weights, loglikes=loglikes, names=[p.name for p in pars],
+                        labels=[p.label if getattr(p, "_label_given", True) else None for p in pars], ignore_rows=0,
+                        ranges=self.ranges, settings=self._current_settings(), device=self._device,
+                        _context_factory=self._context_factory)
+        derived = {p.name: p.isDerived for p in pars}
+        for par in new.paramNames.names:  # (those the constructor kept: a parameter that never moves is a fixed range now)
+            par.isDerived = derived[par.name]
+        return new
+
+    # ---- look-ups and small queries ----------------------------------------------------------------------------
+    def getParamSampleDict(self, ix, want_derived=True, want_fixed=True):
+        """mcsamples.py:2606-2618: the values of sample row ``ix`` by name, with those of the fixed parameters"""
+        res = super().getParamSampleDict(ix, want_derived=want_derived)
+        if want_fixed:
+            res.update(self.ranges.fixedValueDict())
+        return res
+
+    def getParamBestFitDict(self, best_sample=False, want_derived=True, want_fixed=True, max_posterior=True):
+        """mcsamples.py:2578-2604: the best-fit SAMPLE (``best_sample=True``: the row of the smallest loglike, as
+        getParamSampleDict gives it); the best fit of a minimiser's files is outside this package."""
+        if not best_sample:
+            raise NotImplementedError("best-fit files are outside the accelerated path")
+        if not max_posterior:
+            raise ValueError("best_fit_sample is only maximum posterior")
+        if self.loglikes is None:
+            raise ValueError("No likelihoods in samples")
+        return self.getParamSampleDict(np.argmin(self.loglikes))
+
+    def getBounds(self):
+        """mcsamples.py:2293-2309: the hard bounds the samples actually come near (a ParamBounds; a range the samples stay
+        far from is no bound).  The reference reads the flags whatever density call last left them; here the range logic is
+        run for every parameter first, as getMargeStats does."""
+        if self.needs_update:
+            self.updateBaseStatistics()
+        self._init_params(list(range(self.n)))
+        bounds = ParamBounds()
+        bounds.names = self.paramNames.list()
+        for par in self.paramNames.names:
+            if par.has_limits_bot:
+                bounds.lower[par.name] = par.limmin
+            if par.has_limits_top:
+                bounds.upper[par.name] = par.limmax
+        return bounds
+
+    def getCorrelatedVariable2DPlots(self, num_plots=12, nparam=None):
+        """mcsamples.py:2533-2558: [x, y] names of the most correlated pairs among the first ``nparam`` parameters (default:
+        the non-derived ones), strongest first.  The reference's scan: each pick is the largest |correlation| strictly
+        below the previous pick, the first such pair in row order -- so of pairs that tie exactly only one is listed."""
+        if self.needs_update:
+            self.updateBaseStatistics()
+        nparam = nparam or self.paramNames.numNonDerived()
+        ix1, ix2 = np.triu_indices(nparam, 1)
+        vals = np.abs(np.asarray(self.getCorrelationMatrix())[ix1, ix2])
+        pairs, below = [], np.inf
+        for _ in range(num_plots):
+            left = vals < below  # (a NaN correlation never qualifies)
+            if not left.any():
+                break
+            below = vals[left].max()
+            k = int(np.nonzero(vals == below)[0][0])
+            pairs.append([self.parName(int(ix1[k])), self.parName(int(ix2[k]))])
+        return pairs
+
+    def getNumSampleSummaryText(self):
+        """mcsamples.py:887-901: rows, parameters and the measures of the effective number of samples, as text"""
+        if self.needs_update:
+            self.updateBaseStatistics()
+        lines = "using %s rows, %s parameters; mean weight %s, tot weight %s\n" % (
+            self.numrows, self.paramNames.numParams(), self.mean_mult, self.norm)
+        if self.indep_thin != 0:
+            lines += "Approx indep samples (N/corr length): %s\n" % (round(self.norm / self.indep_thin))
+        lines += "Equiv number of single samples (sum w)/max(w): %s\n" % (round(self.norm / self.max_mult))
+        lines += "Effective number of weighted samples (sum w)^2/sum(w^2): %s\n" % (int(self.norm**2 / self._sum_w2))
+        return lines
 
     # ---- likelihood statistics (mcsamples.py:2216-2261, 2369-2378) ----------------------------------------------
     def _setLikeStats(self):

@@ -120,6 +120,32 @@ class ParamNames:
         """paramnames.py:324-332"""
         return {p.name: list(getattr(p, "renames", [])) for p in self.names if keep_empty or getattr(p, "renames", [])}
 
+    def updateRenames(self, renames):
+        """paramnames.py:334-342: merge the mapping {name: alternative name(s)} into the parameters' renames.  Names are
+        alternatives of one another when a chain of entries (the parameters' own and the given ones, keys and values
+        alike) connects them; every parameter ends up with the other names of its group.  The reference keeps a group in
+        a set, so the order of a renames list is not defined there; here a parameter's own renames come first and the new
+        ones follow in the order given."""
+        groups = [[p.name, *getattr(p, "renames", [])] for p in self.names]
+        own = len(groups)
+        for key, alt in (renames or {}).items():
+            groups.append([key, *([alt] if isinstance(alt, str) else list(alt or []))])
+        merged = True
+        while merged:  # join groups that share a name until none do
+            merged = False
+            for a in range(len(groups)):
+                for b in range(a + 1, len(groups)):
+                    if set(groups[a]) & set(groups[b]):
+                        groups[a] += [nm for nm in groups.pop(b) if nm not in groups[a]]
+                        own -= b < own
+                        merged = True
+                        break
+                if merged:
+                    break
+        for group in groups[:own]:  # (two parameters joined into one group: the first one holds the names, as a dict key would)
+            par = self.names[self.numberOfName(group[0])]
+            par.renames = [nm for nm in group if nm != par.name]
+
     def numParams(self):
         return len(self.names)
 

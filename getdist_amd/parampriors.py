@@ -52,6 +52,10 @@ class ParamBounds:
         lo, hi = self.lower.get(name), self.upper.get(name)
         return lo if lo is not None and lo == hi else None
 
+    def fixedValueDict(self):
+        """parampriors.py:130-139: {name: value} of the zero-width ranges"""
+        return {name: self.fixedValue(name) for name in self.names if self.fixedValue(name) is not None}
+
     def getLower(self, name):
         return self.lower.get(name)
 

@@ -86,6 +86,15 @@ int gd_upload(gd_ctx* ctx, const double* X, int64_t N, int64_t n, int64_t row_st
 int gd_num_rows(gd_ctx* ctx, int64_t* N, int64_t* n);
 /* device pointer to column j (N doubles) / weights (NULL if unit) -- for tests and zero-copy users */
 int gd_column_ptr(gd_ctx* ctx, int64_t j, void** d_out);
+/* gd_clone_samples: the device half of MCSamples.copy (mcsamples.py:308-322, copy.deepcopy of a sample set): dst receives
+ *   allocations of its OWN holding src's N x n columns and sample weights (none for a unit-weight set), filled by
+ *   device-to-device copies on dst's stream behind an event recorded on src's stream; the call returns when the copies are
+ *   complete.  dst is then in the state gd_upload of the same data leaves it in (row / column counts, the integral-weights
+ *   flag and the weights' total, no cached prefix sums, bucket or index columns); the spare columns
+ *   (gd_set_extra_column) are NOT copied, and while src has auxiliary weights selected it is src's sample weights that
+ *   are copied.  Nothing is borrowed (unlike gd_attach_samples): src may be re-uploaded or destroyed afterwards.
+ *   GD_ERR_BADARG: dst == src, src without a sample set, contexts on different devices, src borrowing dst's set. */
+int gd_clone_samples(gd_ctx* dst, gd_ctx* src);
 
 /* ---------------------------------------------------------------- weighted moments -------------
  * gd_weight_stats: norm=sum w (chains.py:312), max w (chains.py:1349), sum w^2 (chains.py:499,536),
