@@ -27,7 +27,7 @@ from .chains import Chains, MCSamplesError
 from .densities import Density1D, Density2D, DensitiesError
 from .paramnames import ParamNames
 from .parampriors import ParamBounds
-from .types import LikeStats, MargeStats, ParamLimit
+from .types import LikeStats, MargeStats, NoLineTableFormatter, ParamLimit, ResultTable
 
 # Re-exported: tests, scripts and callers written against getdist_amd.mcsamples import these names from this module; they
 # are defined in chains.py and paramnames.py (the same objects).
@@ -944,6 +944,7 @@ class MCSamples(Chains):
             par.N_eff_kde = None
             par._ranges_done = False
         self._nd_limits_done = False
+        self._marge_done = None
         self.likeStats = None
         self.needs_update = False
 
@@ -1563,19 +1564,56 @@ class MCSamples(Chains):
         self._assign_marge_limits(par, density1D, credible[0], tails[0], max_frac_twotail or self._max_frac_twotail())
 
     def getMargeStats(self, include_bestfit=False):
-        """mcsamples.py:2353-2367: marginalised 1D constraints (numbers only; text tables are out of scope).  All
-        densities, all equal-density intervals and all tail quantiles come from batched device calls."""
+        """mcsamples.py:2353-2367: marginalised 1D constraints.  All densities, all equal-density intervals and all tail
+        quantiles come from batched device calls; the MargeStats returned turns them into text (str(), saveAsText) and
+        LaTeX (texValues; see getTable / getLatex / getInlineLatex) on the host.  Best-fit files are not read."""
         if include_bestfit:
             raise NotImplementedError("best-fit files are outside the accelerated path")
         if self.needs_update:
             self.updateBaseStatistics()
-        dens = self.get1DDensities()  # one batched launch, cached per name
-        mft = self._max_frac_twotail()
-        js = list(range(self.n))
-        credible, tails = self._marge_limit_inputs(js, dens)
-        for j, par in enumerate(self.paramNames.names):
-            self._assign_marge_limits(par, dens[j], credible[j], tails[j], mft)
+        # the limits stay on the parameters until the statistics are recomputed (the reference's done_1Dbins,
+        # mcsamples.py:2449): a table or a plot title per parameter asks for them again and again
+        asked = (tuple(self.contours), self.credible_interval_threshold, bool(getattr(self, "force_twotail", False)),
+                 tuple(sorted(getattr(self, "_max_frac_overrides", {}).items())))
+        if getattr(self, "_marge_done", None) != asked:
+            dens = self.get1DDensities()  # one batched launch, cached per name
+            mft = self._max_frac_twotail()
+            js = list(range(self.n))
+            credible, tails = self._marge_limit_inputs(js, dens)
+            for j, par in enumerate(self.paramNames.names):
+                self._assign_marge_limits(par, dens[j], credible[j], tails[j], mft)
+            self._marge_done = asked
         return MargeStats(self.paramNames.names, self.contours)
+
+    # ---- result text (mcsamples.py:2379-2440): formatting of what getMargeStats brought back, no device call of its own
+    def getTable(self, columns=1, include_bestfit=False, **kwargs):
+        """mcsamples.py:2379-2388: a types.ResultTable of the marginalised constraints in ``columns`` parameter columns;
+        ``kwargs`` go to ResultTable (limit, paramList, titles, formatter, refResults, ...)."""
+        return ResultTable(columns, [self.getMargeStats(include_bestfit)], **kwargs)
+
+    def getLatex(self, params=None, limit=1, err_sig_figs=None):
+        """mcsamples.py:2390-2422: (labels, LaTeX snippets) of the constraints on ``params`` (names or ParamInfo objects;
+        default all) at limit number ``limit``; None entries for names not present.  A single name as a string gives
+        what getInlineLatex gives.  ``err_sig_figs``: significant figures of the errors."""
+        if isinstance(params, str):
+            return self.getInlineLatex(params, limit, err_sig_figs)
+        marge = self.getMargeStats()
+        formatter = NoLineTableFormatter()
+        if err_sig_figs:
+            formatter.numberFormatter.err_sf = err_sig_figs
+        labels, texs = [], []
+        for par in marge.list() if params is None else params:
+            tex = marge.texValues(formatter, par, limit=limit)
+            texs.append(None if tex is None else tex[0])
+            labels.append(None if tex is None else marge.parWithName(par if isinstance(par, str) else par.name).getLabel())
+        return labels, texs
+
+    def getInlineLatex(self, param, limit=1, err_sig_figs=None):
+        """mcsamples.py:2424-2440: ``label = value +- error`` of one parameter, or ``label < value`` for a one-tail limit"""
+        labels, texs = self.getLatex([param], limit, err_sig_figs)
+        if texs[0] is None:
+            raise ValueError("parameter %s not found" % param)
+        return labels[0] + (" " if texs[0][0] in "<>" else " = ") + texs[0]
 
     # ---- 2D densities (mcsamples.py:1285-1419, 1730-2010) ---------------------------------------------------
     def get2DDensity(self, x, y, normalized=False, **kwargs):

@@ -1,7 +1,9 @@
 """
 Parameter names and per-parameter state: ``ParamInfo`` and ``ParamNames``, the parts of getdist/paramnames.py that
-the KDE / weighted-statistics path reads and writes.
+the KDE / weighted-statistics path reads and writes, and the list behaviour the result types share with them.
 """
+
+import copy as _copy
 
 try:
     # GetDist's plotting layer -- the caller this package is a drop-in for -- recognises a parameter object by
@@ -15,7 +17,7 @@ except Exception:  # noqa: BLE001 -- not installed (or not importable): nothing 
 class ParamInfo(_PlotParamInfo):
     """Per-parameter state bag; the attributes the hot path reads and writes (paramnames.py:69-154)."""
 
-    def __init__(self, name, label=None):
+    def __init__(self, name="", label=None):
         if _PlotParamInfo is not object:
             super().__init__(name=name, label=label or name)
         self.name = name
@@ -55,19 +57,52 @@ class ParamInfo(_PlotParamInfo):
         return "ParamInfo(%s)" % self.name
 
 
-class ParamNames:
-    def __init__(self, names, labels=None):
-        labels = labels or [None] * len(names)
-        self.names = [ParamInfo(n, lab) for n, lab in zip(names, labels)]
+class ParamList:
+    """The list behaviour shared by ParamNames and the result types of types.py (paramnames.py:156-416, the part they
+    use): ``names`` is an ordered list of ParamInfo objects."""
 
-    def __str__(self):
-        """paramnames.py:391-395"""
-        return "".join(par.string() + "\n" for par in self.names)
+    def __init__(self):
+        self.names = []
+
+    def list(self):
+        return [p.name for p in self.names]
+
+    def numParams(self):
+        return len(self.names)
 
     def saveAsText(self, filename):
-        """paramnames.py:397-404: write the .paramnames file"""
+        """paramnames.py:397-404: write str(self) -- the .paramnames file of a ParamNames, the .margestats / .likestats
+        text of a result"""
         with open(filename, "w", encoding="utf-8") as f:
             f.write(str(self))
+
+    def fileList(self, fname):
+        """paramnames.py:344-347: the lines of a text file (a byte-order mark is dropped)"""
+        with open(fname, encoding="utf-8-sig") as f:
+            return f.readlines()
+
+    def filteredCopy(self, params):
+        """paramnames.py:352-361: a copy restricted to ``params`` (names, or an object listing them).  The copy is deep --
+        it shares no parameter object with this one -- and follows the order of ``params``; names not present are left
+        out.  (The reference's copy shares the parameter objects and keeps this object's order.)"""
+        wanted = params.list() if hasattr(params, "list") else [getattr(p, "name", p) for p in params]
+        new = _copy.copy(self)
+        new.__dict__ = {k: _copy.deepcopy(v) for k, v in self.__dict__.items() if k != "names"}
+        own = {p.name: p for p in self.names}
+        new.names = [_copy.deepcopy(own[nm]) for nm in wanted if nm in own]
+        return new
+
+    def maxNameLen(self):
+        return max(len(p.name) for p in self.names)
+
+    def parFormat(self):
+        """paramnames.py:380-382: the %-format of the name column of a result file"""
+        return "%-" + str(max(9, self.maxNameLen()) + 1) + "s"
+
+    def name(self, ix, tag_derived=False):
+        """paramnames.py:384-389: name of parameter ``ix``, with a * behind a derived one if asked"""
+        par = self.names[ix]
+        return par.name + "*" if tag_derived and par.isDerived else par.name
 
     def parWithName(self, name, error=False, renames=None):
         """paramnames.py:232-255: the parameter called ``name`` -- by its own name, by one of its ``renames``, or through the
@@ -88,6 +123,16 @@ class ParamNames:
 
             raise ParamError("parameter name not found: %s" % name)
         return None
+
+
+class ParamNames(ParamList):
+    def __init__(self, names, labels=None):
+        labels = labels or [None] * len(names)
+        self.names = [ParamInfo(n, lab) for n, lab in zip(names, labels)]
+
+    def __str__(self):
+        """paramnames.py:391-395"""
+        return "".join(par.string() + "\n" for par in self.names)
 
     def hasParam(self, name):
         return self.numberOfName(name) != -1
@@ -146,9 +191,6 @@ class ParamNames:
             par = self.names[self.numberOfName(group[0])]
             par.renames = [nm for nm in group if nm != par.name]
 
-    def numParams(self):
-        return len(self.names)
-
     def labels(self):
         return [p.label for p in self.names]
 
@@ -157,9 +199,6 @@ class ParamNames:
             if p.name == name:
                 return i
         return -1
-
-    def list(self):
-        return [p.name for p in self.names]
 
     def numNonDerived(self):
         return len([p for p in self.names if not p.isDerived])
