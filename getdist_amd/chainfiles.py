@@ -4,8 +4,10 @@ Chain ingestion: GetDist's plain-text chain format -- ``ro
 per line, ``*`` = derived) and ``root.ranges`` (``name  lower  upper``, ``N`` = unbounded) -- read into a getdist_amd
 MCSamples.  Follows chains.py:77-125 (file matching, loadNumpyTxt), chains.py:228-246 / mcsamples.py:501-528
 (ignore_rows burn-in per chain, fixed-parameter deletion, makeSingle) and paramnames.py / parampriors.py for the two
-side files.  With a device context the parse itself runs on the device (``Context.parse_text``: gd_parse_scan /
-gd_parse_rows, every value bit-equal to np.loadtxt); without one, or for a text the device declines, it is host work:
+side files.  A Cobaya run -- ``root.1.txt, ...`` beside ``root.updated.yaml`` -- is read the same way, its yaml standing in
+for the two side files (cobaya_interface.py, read_root).  With a device context the parse itself runs on the device
+(``Context.parse_text``: gd_parse_scan / gd_parse_rows, every value bit-equal to np.loadtxt); without one, or for a text the
+device declines, it is host work:
 pandas' C tokenizer with ``float_precision="round_trip"`` when present, else np.loadtxt.  (Measured with numpy 2.2.6 on a
 161 MB file, 200 000 x 52 at ``%.8e``: np.loadtxt 1.83 s = 88 MB/s, pandas round_trip 5.18 s = 31 MB/s -- pandas is no
 longer the faster of the two.)  The columns go to the device in the same SoA layout as array input.
@@ -122,14 +124,16 @@ def readParamNames(fname, with_comments=False):
 
 
 def readRanges(fname):
-    """parampriors.py:30-60: name -> (lower, upper) with None for 'N'."""
+    """parampriors.py:30-60, 89-94: name -> (lower, upper) with None for 'N'; (lower, upper, True) for a line with a fourth
+    field that says periodic (what ParamBounds.__str__ writes behind a periodic parameter)."""
     ranges = {}
     with open(fname, encoding="utf-8-sig") as f:
         for line in f:
             parts = line.split()
             if len(parts) >= 3 and not parts[0].startswith("#"):
                 lo, hi = (None if v in ("N", "None") else float(v) for v in parts[1:3])
-                ranges[parts[0]] = (lo, hi)
+                periodic = len(parts) == 4 and parts[3].upper() in ("T", "TRUE", "PERIODIC")
+                ranges[parts[0]] = (lo, hi, True) if periodic else (lo, hi)
     return ranges
 
 
@@ -364,6 +368,13 @@ def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None, ctx=Non
     the chain files (or the binary cache when it is newer than all of them), ``.paramnames`` and ``.ranges``.
     Returns dict(samples=[per-chain (rows, n)], weights=[...], loglikes=[...], names, labels, derived, ranges,
     from_cache).  No burn-in is removed here.  ``ctx`` parses the chain files on the device (loadNumpyTxt).
+
+    A root without ``.paramnames`` beside which cobaya_interface.cobaya_params_file finds a yaml is a Cobaya run
+    (``root.1.txt, ...``): names, labels, derived flags and ``renames`` come from the yaml, matched to the chain columns by
+    position, and -- unless ``root.ranges`` exists -- so do the ranges, of every parameter the yaml lists (a fixed parameter
+    has no column; the ranges of a GetDist-format root are restricted to its columns).  ``info_dict`` is the parsed yaml
+    (None for any other root).  The cache of such a root is also older than any ``*updated.yaml`` / ``*full.yaml`` with
+    the root's prefix.
     """
     from .chains import WeightedSampleError
 
@@ -375,7 +386,15 @@ def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None, ctx=Non
     cpath = cache_path(file_root)
     chains = None
     from_cache = False
-    if not no_cache and os.path.isfile(cpath) and max(os.path.getmtime(f) for f in files) < os.path.getmtime(cpath):
+    getdist_format = os.path.isfile(file_root + ".paramnames")
+    sources = list(files)
+    if not getdist_format:
+        # mcsamples.py:95-101: a Cobaya run's cache is also older than any yaml of the run written since (a resumed or
+        # post-processed run rewrites updated.yaml; the chain rows it describes may have changed with it)
+        folder, prefix = os.path.dirname(file_root) or ".", os.path.basename(file_root)
+        sources += [os.path.join(folder, f) for f in os.listdir(folder)
+                    if f.startswith(prefix) and f.lower().endswith(("updated.yaml", "full.yaml"))]
+    if not no_cache and os.path.isfile(cpath) and max(os.path.getmtime(f) for f in sources) < os.path.getmtime(cpath):
         try:
             block, rows = read_soa_cache(cpath, alloc)
             offs = np.cumsum([0] + list(rows))
@@ -398,17 +417,43 @@ def read_root(file_root, chain_exclude=None, no_cache=False, alloc=None, ctx=Non
             except OSError:
                 pass  # read-only chain directory: the cache is an optimisation only
     n = chains[0].shape[1] - 2
-    labels = derived = comments = None
-    if os.path.isfile(file_root + ".paramnames"):
+    labels = derived = comments = renames = info_dict = None
+    yaml_file = None
+    if getdist_format:
         names, labels, derived, comments = readParamNames(file_root + ".paramnames", with_comments=True)
         if len(names) != n:
             raise WeightedSampleError("paramnames file does not match the number of chain columns")
     else:
-        names = ["param%d" % (i + 1) for i in range(n)]
-    ranges = readRanges(file_root + ".ranges") if os.path.isfile(file_root + ".ranges") else {}
+        from .cobaya_interface import cobaya_params_file
+
+        yaml_file = cobaya_params_file(file_root)
+        if yaml_file:
+            # chains.py:1131-1136: a Cobaya run.  Its parameters are matched to the chain columns by position (the header
+            # line of the chain files is a comment to the parser): sampled first, then derived (ParamNames.loadFromFile)
+            from .paramnames import ParamNames
+
+            pars = ParamNames.fromFile(yaml_file)
+            names, labels = pars.list(), pars.labels()
+            if len(names) != n:
+                raise WeightedSampleError("the parameters of %s do not match the number of chain columns" % os.path.basename(yaml_file))
+            derived = [p.isDerived for p in pars.names]
+            renames, info_dict = pars.getRenames(), pars.info_dict
+        else:
+            names = ["param%d" % (i + 1) for i in range(n)]
+    if os.path.isfile(file_root + ".ranges"):  # mcsamples.py:2280-2291: the .ranges file, else the run's yaml
+        ranges = readRanges(file_root + ".ranges")
+        if yaml_file is None:
+            ranges = {k: v for k, v in ranges.items() if k in names}
+    elif yaml_file:
+        from .cobaya_interface import get_info_params, get_range
+
+        # every entry, not only the chain's columns: a fixed parameter has no column and is a zero-width range
+        ranges = {p: get_range(entry) for p, entry in get_info_params(info_dict).items()}
+    else:
+        ranges = {}
     return dict(samples=[c[:, 2:] for c in chains], weights=[c[:, 0] for c in chains], loglikes=[c[:, 1] for c in chains],
-                names=names, labels=labels, derived=derived, comments=comments, ranges={k: v for k, v in ranges.items() if k in names},
-                from_cache=from_cache)
+                names=names, labels=labels, derived=derived, comments=comments, ranges=ranges, renames=renames,
+                info_dict=info_dict, from_cache=from_cache)
 
 
 def loadMCSamples(file_root, ini=None, jobItem=None, no_cache=False, settings=None, chain_exclude=None, **kwargs):

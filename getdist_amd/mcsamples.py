@@ -242,12 +242,15 @@ class MCSamples(Chains):
     """
     Weighted samples resident in HBM + the KDE hot path.  Constructor arguments follow
     mcsamples.py:149-161 (``samples`` may be an (N, n) array or a list of per-chain arrays;
-    ``ranges`` maps name -> (lower, upper[, True|'periodic'])).  ``device`` selects the GPU.
+    ``ranges`` maps name -> (lower, upper[, True|'periodic'])).  ``device`` selects the GPU.  ``renames`` maps names to
+    alternative name(s) (chains.py:1139-1140); a name given as ``"x*"`` is the derived parameter ``x``.  With ``root`` of a
+    Cobaya run (chainfiles.read_root) the run's yaml also gives label, sampler and temperature where none was passed
+    (_cobaya_properties); unlike the reference, a sampler that comes out as "nested" this way refuses ``ignore_rows`` too.
     """
 
     def __init__(self, root=None, ini=None, settings=None, ranges=None, samples=None, weights=None, loglikes=None,
                  temperature=None, names=None, labels=None, label=None, name_tag=None, sampler=None, device=0,
-                 _context_factory=None, **kwargs):
+                 _context_factory=None, renames=None, **kwargs):
         self.sampler = sampler or "mcmc"
         self.temperature, self.cooled = temperature, 1
         self._likeStats = None
@@ -281,7 +284,7 @@ class MCSamples(Chains):
         if self.sampler == "nested" and not np.isclose(self.ignore_rows, 0):
             raise ValueError("Should not remove burn-in from Nested Sampler samples.")
         self.ranges = ParamBounds()
-        derived = comments = None
+        derived = comments = info_dict = file_renames = None
         if root is not None and samples is None:
             # mcsamples.py:47-146, chains.py:1368-1405: the chain files, side files and (when fresh) the binary cache
             from . import chainfiles
@@ -296,6 +299,15 @@ class MCSamples(Chains):
             for nm, rng in loaded["ranges"].items():
                 self.ranges.setRange(nm, rng)
             self.name_tag = self.name_tag or os.path.basename(root)
+            info_dict = loaded.get("info_dict")
+            if info_dict is not None:
+                file_renames = loaded["renames"]
+                if not os.path.exists(root + ".properties.ini"):
+                    self._cobaya_properties(info_dict, sampler is None)
+        elif names is not None and any(isinstance(nm, str) and nm.endswith("*") for nm in names):
+            # paramnames.py:97-111 through chains.py:1170-1172: a name given as "x*" is the derived parameter x
+            derived = [nm.endswith("*") for nm in names]
+            names = [nm[:-1] if d else nm for nm, d in zip(names, derived)]
         ignore_lines = int(self.ignore_rows)
         if samples is None:
             raise MCSamplesError("samples are required")
@@ -315,6 +327,10 @@ class MCSamples(Chains):
         if len(names) != n_all:
             raise MCSamplesError("names do not match the number of sample columns")
         self.paramNames = ParamNames(list(names), labels)
+        self.paramNames.info_dict = info_dict
+        for more in (file_renames, renames):  # those of a Cobaya run's yaml, then the keyword's (chains.py:1139-1140)
+            if more:
+                self.paramNames.updateRenames(more)
         if derived is not None:
             for par, d in zip(self.paramNames.names, derived):
                 par.isDerived = bool(d)
@@ -347,6 +363,40 @@ class MCSamples(Chains):
         self.needs_update = True
         self._upload(filter_weights=False)  # the per-chain filter already ran (makeSingle passes min_weight_ratio=-1)
         self.updateBaseStatistics()
+
+    def _cobaya_properties(self, info, want_sampler):
+        """mcsamples.py:285-303: what a Cobaya run's yaml says about the chain, for a root without a .properties.ini.  Rows
+        the run reports as removed already (cobaya_interface.get_burn_removed) are not removed again; the run's label is
+        taken if none was given, its sampler if none was passed (``want_sampler``; setSampler, chains.py:1147-1152: an
+        unknown one warns and counts as mcmc) and its temperature if none was passed.  ``self.properties`` records all of it
+        -- the temperature only when it is not 1 -- and that a burn-in is (or was) removed."""
+        from . import cobaya_interface as ci
+
+        self.properties = {}
+        if ci.get_burn_removed(info):
+            self.properties["burn_removed"] = True
+            self.ignore_rows = 0.0
+        if not self.label:
+            self.label = ci.get_sample_label(info)
+            if self.label:
+                self.properties["label"] = self.label
+        if want_sampler:
+            sampler = ci.get_sampler_type(info).lower()
+            if sampler not in ("mcmc", "nested", "uncorrelated"):
+                import warnings
+
+                warnings.warn("Unknown sampler type %s. Assuming MCMC." % sampler)
+                sampler = "mcmc"
+            self.sampler = sampler
+            if sampler == "nested" and not np.isclose(self.ignore_rows, 0):  # (the check of the constructor, for this sampler)
+                raise ValueError("Should not remove burn-in from Nested Sampler samples.")
+        self.properties["sampler"] = self.sampler
+        if self.temperature is None:
+            self.temperature = ci.get_sampler_temperature(info)
+        if self.temperature is not None and self.temperature != 1:
+            self.properties["temperature"] = self.temperature
+        if self.ignore_rows:
+            self.properties["burn_removed"] = True
 
     def _read_chains(self, samples, weights, loglikes, ignore_lines):
         """

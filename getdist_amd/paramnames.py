@@ -126,9 +126,56 @@ class ParamList:
 
 
 class ParamNames(ParamList):
+    info_dict = None          # the parsed yaml of a Cobaya run, when the names were loaded from one (paramnames.py:451)
+    filenameLoadedFrom = ""   # paramnames.py:436: the file's name without its folder
+
     def __init__(self, names, labels=None):
         labels = labels or [None] * len(names)
         self.names = [ParamInfo(n, lab) for n, lab in zip(names, labels)]
+
+    @classmethod
+    def fromFile(cls, fileName):
+        """A ParamNames loaded from a ``.paramnames`` file or from the yaml file of a Cobaya run (loadFromFile)"""
+        new = cls([])
+        new.loadFromFile(fileName)
+        return new
+
+    def loadFromFile(self, fileName):
+        """paramnames.py:431-470: replace the parameters by those of a file.
+
+        ``.paramnames``: one ``name[*]  label  [# comment]`` line per parameter (chainfiles.readParamNames).
+        ``.yaml`` / ``.yml`` (a Cobaya ``updated.yaml``): the entries of cobaya_interface.get_info_params, the sampled
+        parameters first and then the derived ones, each in the order of the file -- the order of the columns of the run's
+        chain files; fixed parameters are neither.  The label is the entry's ``latex`` (the name if it has none), renames
+        its ``renames``.  The parsed file is kept as ``info_dict``.  Any other suffix raises ValueError."""
+        import os
+
+        extension = os.path.splitext(fileName)[-1]
+        if extension == ".paramnames":
+            from .chainfiles import readParamNames
+
+            names, labels, derived, comments = readParamNames(fileName, with_comments=True)
+            self.names = [ParamInfo(n, lab) for n, lab in zip(names, labels)]
+            for par, d, c in zip(self.names, derived, comments):
+                par.isDerived, par.comment = d, c
+        elif extension.lower() in (".yaml", ".yml"):
+            from . import cobaya_interface as ci
+            from .yaml_tools import yaml_load_file
+
+            self.info_dict = yaml_load_file(fileName)
+            entries = ci.get_info_params(self.info_dict)
+            self.names = []
+            for derived, wanted in ((False, ci.is_sampled_param), (True, ci.is_derived_param)):
+                for name, entry in entries.items():
+                    if wanted(entry):
+                        par = ParamInfo(name, (entry or {}).get(ci._p_label, name))
+                        alts = (entry or {}).get(ci._p_renames) or []
+                        par.renames = [alts] if isinstance(alts, str) else list(alts)
+                        par.isDerived = derived
+                        self.names.append(par)
+        else:
+            raise ValueError("ParanNames must be loaded from .paramnames or .yaml/.yml file, found %s" % fileName)
+        self.filenameLoadedFrom = os.path.split(fileName)[1]
 
     def __str__(self):
         """paramnames.py:391-395"""

@@ -5,9 +5,35 @@
 class ParamBounds:
     """Hard prior ranges and periodic flags (parampriors.py:6-139, the parts the hot path uses)."""
 
-    def __init__(self):
+    def __init__(self, fileName=None):
         self.lower, self.upper, self.periodic = {}, {}, set()
         self.names = []  # in the order the ranges were first set: the order of the lines of a .ranges file
+        if fileName is not None:
+            self.loadFromFile(fileName)
+
+    def loadFromFile(self, fileName):
+        """parampriors.py:27-43: add the ranges of a file.
+
+        ``.ranges`` / ``.bounds``: ``name  lower  upper  [periodic]`` lines, ``N`` for an open side (chainfiles.readRanges).
+        ``.yaml`` / ``.yml`` (a Cobaya ``updated.yaml``): cobaya_interface.get_range of every entry of get_info_params, so
+        the fixed parameters -- which no chain column holds -- come in as zero-width ranges.  Any other suffix raises
+        ValueError."""
+        import os
+
+        extension = os.path.splitext(fileName)[-1]
+        if extension in (".ranges", ".bounds"):
+            from .chainfiles import readRanges
+
+            for name, rng in readRanges(fileName).items():
+                self.setRange(name, rng)
+        elif extension in (".yaml", ".yml"):
+            from .cobaya_interface import get_info_params, get_range
+
+            for name, entry in get_info_params(fileName).items():
+                self.setRange(name, get_range(entry))
+        else:
+            raise ValueError("ParamBounds must be loaded from .bounds, .ranges or .yaml/.yml file, not %s" % fileName)
+        self.filenameLoadedFrom = os.path.split(fileName)[1]
 
     def __str__(self):
         """parampriors.py:45-63: one line per parameter, ``%22s%17s%17s`` of name, lower, upper (``%15.7E``, or N for an open
