@@ -158,6 +158,7 @@ SIGNATURES = {
     "gd_format_matrix": (C.c_int, [_p, _p, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _p, _i64, _pi64]),
     "gd_parse_scan": (C.c_int, [_p, _p, _i64, _i32, _pi64, _pi32, _pi64]),
     "gd_parse_rows": (C.c_int, [_p, _p, _i64, _i32, _i64, _i32, _p, _i64, _i64, _p, _i64, _pi64]),
+    "gd_expr_eval": (C.c_int, [_p, _pi32, _i32, _pd, _i32, _i32, _i32, _i64, _i64, _p, _pd]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
@@ -169,6 +170,11 @@ GD_FMT_SRC_WEIGHT, GD_FMT_SRC_ZERO, GD_FMT_SRC_ONE = -1, -2, -3
 GD_FMT_MAX_PREC, GD_FMT_MAX_WIDTH = 17, 32
 GD_PARSE_NOT_PLAIN = -23
 GD_PARSE_MAX_LINE = 8192
+GD_EX_MAX_CODE, GD_EX_MAX_STACK, GD_EX_MAX_CONST, GD_EX_MAX_COLS = 128, 16, 32, 16
+GD_EX_WEIGHT = -1
+GD_EX_OPS = ("COL CONST NEG ABS SQRT SQUARE RECIP EXP LOG LOG10 LOG2 SIN COS TAN ATAN TANH NOT ADD SUB MUL DIV POW ATAN2 MIN MAX "
+             "LT LE GT GE EQ NE AND OR WHERE").split()  # GD_EX_<name> = its position
+GD_EX_TO_COLUMN, GD_EX_TO_AUXW, GD_EX_TO_HOST_F64, GD_EX_TO_HOST_U8 = 0, 1, 2, 3
 
 
 def format_field_bytes(width, prec):
@@ -782,6 +788,24 @@ class Context:
         if w.shape != (self.N,):
             raise ValueError("weights must have one entry per sample row")
         self._check(self.lib.gd_aux_weights(self.h, _dp(w)))
+
+    def expr_eval(self, code, consts, dst, dst_arg=0, lo=0, hi=None, stats=False):
+        """Evaluate the postfix program ``code`` ((ncode, 2) int32 of (op, arg), constants ``consts``) over the rows [lo, hi)
+        of the resident columns (gd_expr_eval).  ``dst``: GD_EX_TO_COLUMN (spare slot ``dst_arg``; returns the column index
+        n + dst_arg), GD_EX_TO_AUXW (the auxiliary weight buffer receives sample weight * value; returns None),
+        GD_EX_TO_HOST_F64 / GD_EX_TO_HOST_U8 (returns the hi - lo values as float64 / as bytes value != 0: views of
+        page-locked memory that the context recycles).  With ``stats`` the result is (that, [min, max, non-zero, NaNs])."""
+        code = np.ascontiguousarray(code, dtype=np.int32).reshape(-1, 2)
+        consts = _f64arr(consts).ravel()
+        hi = self.N if hi is None else int(hi)
+        out = None
+        if dst in (GD_EX_TO_HOST_F64, GD_EX_TO_HOST_U8):
+            out = self.pinned_array((max(hi - int(lo), 0),), np.float64 if dst == GD_EX_TO_HOST_F64 else np.uint8)
+        st = np.zeros(4) if stats else None
+        self._check(self.lib.gd_expr_eval(self.h, _ip(code), len(code), _dp(consts), consts.size, int(dst), int(dst_arg), int(lo),
+                                          hi, None if out is None else out.ctypes.data, None if st is None else _dp(st)))
+        res = self.n + int(dst_arg) if dst == GD_EX_TO_COLUMN else out
+        return (res, st) if stats else res
 
     def col_minmax(self, cols, lo=0, hi=None, cond_col=-1, cond_below=0.0):
         """min / max per column over the rows whose ``cond_col`` value is < ``cond_below`` (cond_col < 0: all rows)."""

@@ -29,6 +29,13 @@ class ParamError(MCSamplesError):
     pass
 
 
+def _is_expr(x):
+    """A colexpr.ColumnExpr?  Tested before any ``==`` / ``in`` on a parameter argument: on an expression those build nodes."""
+    from .colexpr import ColumnExpr
+
+    return isinstance(x, ColumnExpr)
+
+
 def _where_rows(where, numrows):
     """Row indices of a ``where=`` index array with numpy's semantics of x[where]: negative indices count from the end,
     anything outside [-numrows, numrows) raises IndexError (it used to wrap around silently)."""
@@ -196,7 +203,12 @@ class WeightedSamples:
                               None if self.loglikes is None else self.loglikes[rows], offsets)
 
     def filter(self, where):
-        """chains.py:968-979,1174-1186: keep the rows ``where`` (boolean mask or row indices)"""
+        """chains.py:968-979,1174-1186: keep the rows ``where`` (boolean mask, row indices, or a boolean column expression,
+        whose mask is fetched from the device as bytes)"""
+        if _is_expr(where):
+            if not where.is_bool:
+                raise WeightedSampleError("filter takes a boolean expression (a comparison), not a float one")
+            where = where.eval(self)
         where = np.asarray(where)
         offsets = None
         if self.chain_offsets is not None:
@@ -219,7 +231,10 @@ class WeightedSamples:
                 self.filter(self.weights > mx * min_weight_ratio)
 
     def reweightAddingLogLikes(self, logLikes):
-        """chains.py:981-993: importance-sample by adding ``logLikes`` (-log likelihood per sample)"""
+        """chains.py:981-993: importance-sample by adding ``logLikes`` (-log likelihood per sample; a host vector or a column
+        expression, which is evaluated on the device and fetched)"""
+        if _is_expr(logLikes):
+            logLikes = logLikes.eval(self)
         logLikes = np.asarray(logLikes, dtype=np.float64)
         if logLikes.shape != (self.numrows,):
             raise WeightedSampleError("logLikes must have one entry per sample")
@@ -348,8 +363,14 @@ class WeightedSamples:
         return None
 
     def _vec_col(self, par, slot=0):
-        """Device column index for a parameter reference or a host vector (uploaded into spare column ``slot``)."""
-        vec = par.vec if isinstance(par, ParamConfidenceData) else self._host_vector(par)
+        """Device column index for a parameter reference, a host vector (uploaded into spare column ``slot``) or a column
+        expression (evaluated into that slot on the device, colexpr.py).  An expression that reads the loglikes has them
+        made resident in their usual slot, the last one, first: such a call has one slot fewer."""
+        vec = par.vec if isinstance(par, ParamConfidenceData) else (par if _is_expr(par) else self._host_vector(par))
+        if _is_expr(vec):
+            if slot >= self.ctx.EXTRA_COLS - (1 if vec.uses_loglikes() else 0):
+                raise WeightedSampleError("at most %d vector arguments per call" % self.ctx.EXTRA_COLS)
+            return vec.to_column(self, slot)
         if vec is not None:
             if slot >= self.ctx.EXTRA_COLS:
                 raise WeightedSampleError("at most %d vector arguments per call" % self.ctx.EXTRA_COLS)
@@ -369,6 +390,9 @@ class WeightedSamples:
     def _with_weights(self, w_host, fn):
         """Run ``fn`` with the auxiliary weight vector ``w_host`` selected on the device."""
         self.ctx.aux_weights(w_host)
+        return self._with_aux_selected(fn)
+
+    def _with_aux_selected(self, fn):
         self._like_mode = None  # the auxiliary buffer is shared with the like weights
         self.ctx.select_weights(1)
         try:
@@ -376,10 +400,24 @@ class WeightedSamples:
         finally:
             self.ctx.select_weights(0)
 
+    def _where_expr_weights(self, where):
+        """weights*mask of a boolean column expression, formed in the auxiliary weight buffer on the device."""
+        if not where.is_bool:
+            raise WeightedSampleError("where= takes a boolean expression (a comparison), not a float one")
+        self._like_mode = None  # the auxiliary buffer is shared with the like weights: forget them BEFORE it is overwritten,
+        where.to_aux_weights(self)  # so that an error raised between here and the selection leaves no stale claim on it
+
+    def _with_where(self, where, fn):
+        """Run ``fn`` over the rows ``where`` selects: a boolean column expression, a boolean mask or an index array."""
+        if _is_expr(where):
+            self._where_expr_weights(where)
+            return self._with_aux_selected(fn)
+        return self._with_weights(self._where_weights(where), fn)
+
     def get_norm(self, where=None):
         if where is None:
             return self.norm
-        return self._with_weights(self._where_weights(where), lambda: self.ctx.weight_stats()["norm"])
+        return self._with_where(where, lambda: self.ctx.weight_stats()["norm"])
 
     def weighted_sum(self, paramVec, where=None):
         """chains.py:636-649"""
@@ -405,16 +443,20 @@ class WeightedSamples:
 
     def _moments(self, pars, where):
         """(means, cov, norm) of parameter references / vectors, optionally over a row filter: one gd_cov call."""
+        if _is_expr(where):  # first: a mask that reads the loglikes borrows the last spare column while it is evaluated
+            self._where_expr_weights(where)
         slot = 0
         cols = []
         for p in pars:
-            if self._host_vector(p) is not None:
+            if _is_expr(p) or self._host_vector(p) is not None:
                 cols.append(self._vec_col(p, slot))
                 slot += 1
             else:
                 cols.append(self._col(p))
         if where is None:
             return self.ctx.cov(cols)
+        if _is_expr(where):
+            return self._with_aux_selected(lambda: self.ctx.cov(cols))
         return self._with_weights(self._where_weights(where), lambda: self.ctx.cov(cols))
 
     def cov(self, pars=None, where=None):
@@ -444,13 +486,16 @@ class WeightedSamples:
         return j
 
     def _is_plain_column(self, par):
-        return self._host_vector(par) is None
+        return not _is_expr(par) and self._host_vector(par) is None
 
     def mean(self, paramVec, where=None):
         """chains.py:665-677"""
         if isinstance(paramVec, (list, tuple)):
             if where is None and all(self._is_plain_column(p) for p in paramVec):
                 return np.array([self.means[self._col(p)] for p in paramVec])
+            if _is_expr(where):  # the mask is evaluated once for the whole list
+                self._where_expr_weights(where)
+                return self._with_aux_selected(lambda: np.array([self._moments([p], None)[0][0] for p in paramVec]))
             return np.array([self.mean(p, where) for p in paramVec])
         if where is None and self._is_plain_column(paramVec):
             return self.means[self._col(paramVec)]
@@ -469,12 +514,12 @@ class WeightedSamples:
 
     def mean_diff(self, paramVec, where=None):
         """chains.py:744-761 (host vector p_i - mean; the device path never materialises it)"""
-        vec = self._host_vector(paramVec)
+        vec = paramVec.eval(self) if _is_expr(paramVec) else self._host_vector(paramVec)
         if vec is None:
             vec = self.samples[:, self._col(paramVec)]
         if where is None:
             return vec - self.mean(paramVec)
-        return vec[where] - self.mean(paramVec, where)
+        return vec[where.eval(self) if _is_expr(where) else where] - self.mean(paramVec, where)
 
     def mean_diffs(self, pars=None, where=None):
         """chains.py:763-780"""
@@ -487,7 +532,8 @@ class WeightedSamples:
         if isinstance(paramVec, ParamConfidenceData):
             start, end = paramVec.start, paramVec.end
             weights = paramVec.weights if weights is None else weights
-        vec_arg = paramVec.vec if isinstance(paramVec, ParamConfidenceData) else self._host_vector(paramVec)
+        vec_arg = paramVec.vec if isinstance(paramVec, ParamConfidenceData) else (
+            paramVec if _is_expr(paramVec) else self._host_vector(paramVec))
         j = self._vec_col(paramVec)
         limfrac = np.atleast_1d(np.asarray(limfrac, dtype=np.float64))
         end = self.numrows if end is None else end
@@ -517,7 +563,7 @@ class WeightedSamples:
         chains.py:793-812.  The reference caches argsort + cumulative weights here; the device path selects
         quantiles without sorting, so the "cache" is just the (column, row range) handle confidence() accepts.
         """
-        vec = self._host_vector(paramVec)
+        vec = paramVec if _is_expr(paramVec) else self._host_vector(paramVec)  # (an expression is kept as the handle's vec)
         return ParamConfidenceData(None if vec is not None else self._col(paramVec), start,
                                    self.numrows if end is None else end, weights=weights, vec=vec)
 
@@ -640,15 +686,24 @@ class WeightedSamples:
         s = int(nearestFFTnumber(2 * self.numrows))
         return self.ctx.autoconvolve(s, k0 + nlags, False, col=col, mean=mean, use_weights=self.weights is not None)[k0:]
 
+    def _mean_var_of(self, par, col, want_var=True):
+        """(mean, variance) of ``par``, which _vec_col has just placed in device column ``col``.  An expression is not
+        evaluated again for them: one gd_cov over the column it sits in, the call mean() and var() would each end in."""
+        if _is_expr(par):
+            means, cov, _ = self.ctx.cov([col])
+            return means[0], cov[0, 0]
+        return self.mean(par), (self.var(par) if want_var else None)
+
     def getAutocorrelation(self, paramVec, maxOff=None, weight_units=True, normalized=True):
         """chains.py:423-447; ``paramVec`` may be a parameter or a vector of one value per sample"""
         j = self._vec_col(paramVec)
         if maxOff is None:
             maxOff = self.n - 1
-        lags = self._autocov(j, self.mean(paramVec), 0, maxOff + 1)
+        mean, var = self._mean_var_of(paramVec, j, normalized)
+        lags = self._autocov(j, mean, 0, maxOff + 1)
         corr = lags / np.arange(self.numrows, self.numrows - (maxOff + 1), -1)
         if normalized:
-            corr /= self.var(paramVec)
+            corr /= var
         if weight_units:
             return corr * self.numrows / self.norm
         return corr
@@ -662,7 +717,7 @@ class WeightedSamples:
             ix = int(np.argmin(corr > min_corr * corr[0]))
             return corr[0] + 2 * np.sum(corr[1:ix])
         col = self._vec_col(j)
-        mean, var = self.mean(j), self.var(j)
+        mean, var = self._mean_var_of(j, col)
         max_off = self.numrows // 10
         scale = (self.numrows / self.norm) if weight_units else 1.0
         vals = np.zeros(0)
@@ -880,9 +935,12 @@ class Chains(WeightedSamples):
         raise ParamError("Unknown parameter type %s" % name)
 
     def addDerived(self, paramVec, name, label="", comment="", range=None):
-        """mcsamples.py:2560-2575 + chains.py:1354-1366: append a derived parameter column.  Returns its ParamInfo."""
+        """mcsamples.py:2560-2575 + chains.py:1354-1366: append a derived parameter column (a host vector, or a column
+        expression evaluated on the device and fetched).  Returns its ParamInfo."""
         if self.paramNames.parWithName(name):
             raise ValueError("Parameter with name %s already exists" % name)
+        if _is_expr(paramVec):
+            paramVec = paramVec.eval(self)
         vec = np.asarray(paramVec, dtype=np.float64).reshape(-1)
         if vec.shape != (self.numrows,):
             raise WeightedSampleError("derived parameter vector must have one entry per sample")
@@ -924,6 +982,10 @@ class Chains(WeightedSamples):
         """chains.py:1264-1289: give ``obj`` one attribute per parameter name holding its sample vector.  A dotted name
         aa.bb.cc becomes obj.aa.bb.cc through ParSamples sub-objects; a parameter aa whose name is also the head of a dotted
         one is reached as obj.aa.value.  Returns ``obj``."""
+        return self._set_param_attrs(obj, lambda j, par: self.samples[:, j])
+
+    def _set_param_attrs(self, obj, value_of):
+        """The attribute layout of setParams with ``value_of(j, par)`` as the value of parameter j"""
         holders = []
         for par in self.paramNames.names:  # every sub-object first: whether a name holds one does not depend on the order
             *heads, leaf = par.name.split(".")
@@ -935,14 +997,23 @@ class Chains(WeightedSamples):
             holders.append((holder, leaf))
         for j, (holder, leaf) in enumerate(holders):
             if isinstance(getattr(holder, leaf, None), ParSamples):
-                getattr(holder, leaf).value = self.samples[:, j]
+                getattr(holder, leaf).value = value_of(j, self.paramNames.names[j])
             else:
-                setattr(holder, leaf, self.samples[:, j])
+                setattr(holder, leaf, value_of(j, self.paramNames.names[j]))
         return obj
 
     def getParams(self):
         """chains.py:1291-1301: a ParSamples with one attribute per parameter name holding its sample vector"""
         return self.setParams(ParSamples())
+
+    def getDeviceParams(self):
+        """getParams() with a column-expression leaf (colexpr.col(name)) in place of every host vector, same attribute
+        layout: arithmetic on the attributes builds expressions that mean / confidence / addDerived / ``where=`` evaluate
+        on the device.  The leaves hold names, not data: they stay valid across mutators and for other sample sets with
+        the same parameter names.  Not in the reference."""
+        from .colexpr import col
+
+        return self._set_param_attrs(ParSamples(), lambda j, par: col(par.name))
 
     def getParamSampleDict(self, ix, want_derived=True):
         """chains.py:1303-1317: {"weight", "loglike", parameter name: value} of sample row ``ix`` (the weight of a unit-weight

@@ -580,6 +580,92 @@ int gd_parse_scan(gd_ctx* ctx, const void* d_text, int64_t nbytes, int32_t last,
 int gd_parse_rows(gd_ctx* ctx, const void* d_text, int64_t nbytes, int32_t last, int64_t rows, int32_t m, void* d_out, int64_t ld,
                   int64_t row_offset, void* d_fix, int64_t fix_capacity, int64_t* fix_count_out);
 
+/* ---------------------------------------------------------------- column expressions ------------
+ * gd_expr_eval: one fused pass that evaluates a postfix program per sample row over resident columns (colexpr.ColumnExpr:
+ * the derived vector  p.sigma8 * np.sqrt(p.omegam / 0.3)  and the mask  p.H0 > 70  of the GetDist idiom, without host
+ * arithmetic and without an N-vector crossing PCIe).  Not in the reference, which forms such vectors with numpy.
+ * `code` holds ncode (op, arg) pairs of int32; `consts` the nconst doubles GD_EX_CONST refers to.
+ *   GD_EX_COL    pushes column `arg` of the row: a resident column, spare columns n + slot included, or GD_EX_WEIGHT = the
+ *                sample weights (1.0 for a unit-weight set; the sample weights also while auxiliary weights are selected,
+ *                as in gd_format_rows).
+ *   GD_EX_CONST  pushes consts[arg].
+ *   unary ops    replace the top:  NEG (flips the sign bit), ABS (clears it), SQRT, SQUARE (x * x), RECIP (1 / x), EXP, LOG,
+ *                LOG10, LOG2, SIN, COS, TAN, ATAN, TANH, NOT (x == 0 ? 1 : 0).
+ *   binary ops   pop b, then a, and push:  ADD SUB MUL DIV POW ATAN2(a, b), MIN / MAX (a NaN operand gives NaN: numpy's
+ *                minimum / maximum, not fmin / fmax), LT LE GT GE EQ NE (1.0 / 0.0; with a NaN operand false, NE true),
+ *                AND / OR of (a != 0), (b != 0).
+ *   GD_EX_WHERE  pops b, a, c and pushes c != 0 ? a : b.
+ * + - * / sqrt are the IEEE operations (the library is built with -ffp-contract=off: nothing is fused), so programs of
+ * the ops up to MAX, the comparisons, logic and WHERE give numpy's values bit for bit; the transcendental ops are the
+ * device library's.  Division by zero and invalid operands give inf / NaN silently (no warning channel).
+ * Limits: ncode <= GD_EX_MAX_CODE, stack depth <= GD_EX_MAX_STACK, nconst <= GD_EX_MAX_CONST, and at most GD_EX_MAX_COLS
+ * distinct GD_EX_COL arguments (GD_EX_WEIGHT counts as one).
+ * Destination `dst`:
+ *   GD_EX_TO_COLUMN    spare column slot dst_arg (addressed as column n + dst_arg afterwards); may be a slot the program
+ *                      reads (rows are independent).
+ *   GD_EX_TO_AUXW      the auxiliary weight buffer receives sample weight * value -- what gd_aux_weights takes from the
+ *                      host; created and zeroed as there, refused while gd_select_weights(ctx, 1) is in force.
+ *   GD_EX_TO_HOST_F64  host_out receives the hi - lo values as doubles.
+ *   GD_EX_TO_HOST_U8   host_out receives one byte per row, value != 0.
+ * The device destinations cover every row: they need lo = 0, hi = N, write only rows < N (the zero padding up to the
+ * leading dimension stays zero) and return once the kernel has run; the host ones take any [lo, hi) and block until
+ * host_out is filled (page-locked memory for a full-rate copy).
+ * stats_out (may be NULL) receives {minimum, maximum, number of non-zero values, number of NaNs} of the evaluated rows;
+ * minimum and maximum are NaN when a value is NaN (np.min / np.max).  Per-block partials added on the host in block
+ * order, no floating-point atomics: reruns are bit-identical.
+ * GD_ERR_BADARG before any launch: a null argument, no samples uploaded, an empty or out-of-range row range (or one that
+ * is not [0, N) for a device destination), ncode or nconst out of range, an unknown op, a column, constant or slot out
+ * of range, too many distinct columns, stack underflow, depth above GD_EX_MAX_STACK, or a final depth other than 1.
+ * One kernel: 256 threads, two rows per lane (16-byte loads), the program in the kernel arguments (scalar instruction
+ * fetch, wave-uniform dispatch), the columns it reads staged per block in LDS, the evaluation stack with its top in
+ * registers and the rest in LDS as [depth][thread]; grid-stride over at most 2048 blocks. */
+#define GD_EX_MAX_CODE 128
+#define GD_EX_MAX_STACK 16
+#define GD_EX_MAX_CONST 32
+#define GD_EX_MAX_COLS 16
+#define GD_EX_WEIGHT (-1)
+#define GD_EX_COL 0
+#define GD_EX_CONST 1
+#define GD_EX_NEG 2
+#define GD_EX_ABS 3
+#define GD_EX_SQRT 4
+#define GD_EX_SQUARE 5
+#define GD_EX_RECIP 6
+#define GD_EX_EXP 7
+#define GD_EX_LOG 8
+#define GD_EX_LOG10 9
+#define GD_EX_LOG2 10
+#define GD_EX_SIN 11
+#define GD_EX_COS 12
+#define GD_EX_TAN 13
+#define GD_EX_ATAN 14
+#define GD_EX_TANH 15
+#define GD_EX_NOT 16
+#define GD_EX_ADD 17
+#define GD_EX_SUB 18
+#define GD_EX_MUL 19
+#define GD_EX_DIV 20
+#define GD_EX_POW 21
+#define GD_EX_ATAN2 22
+#define GD_EX_MIN 23
+#define GD_EX_MAX 24
+#define GD_EX_LT 25
+#define GD_EX_LE 26
+#define GD_EX_GT 27
+#define GD_EX_GE 28
+#define GD_EX_EQ 29
+#define GD_EX_NE 30
+#define GD_EX_AND 31
+#define GD_EX_OR 32
+#define GD_EX_WHERE 33
+#define GD_EX_NUM_OPS 34
+#define GD_EX_TO_COLUMN 0
+#define GD_EX_TO_AUXW 1
+#define GD_EX_TO_HOST_F64 2
+#define GD_EX_TO_HOST_U8 3
+int gd_expr_eval(gd_ctx* ctx, const int32_t* code, int32_t ncode, const double* consts, int32_t nconst, int32_t dst,
+                 int32_t dst_arg, int64_t lo, int64_t hi, void* host_out, double* stats_out);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
