@@ -159,6 +159,7 @@ SIGNATURES = {
     "gd_parse_scan": (C.c_int, [_p, _p, _i64, _i32, _pi64, _pi32, _pi64]),
     "gd_parse_rows": (C.c_int, [_p, _p, _i64, _i32, _i64, _i32, _p, _i64, _i64, _p, _i64, _pi64]),
     "gd_expr_eval": (C.c_int, [_p, _pi32, _i32, _pd, _i32, _i32, _i32, _i64, _i64, _p, _pd]),
+    "gd_expr_eval_tab": (C.c_int, [_p, _pi32, _i32, _pd, _i32, _i32, _i32, _i64, _i64, _p, _pd, _p, _i32]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
@@ -175,6 +176,28 @@ GD_EX_WEIGHT = -1
 GD_EX_OPS = ("COL CONST NEG ABS SQRT SQUARE RECIP EXP LOG LOG10 LOG2 SIN COS TAN ATAN TANH NOT ADD SUB MUL DIV POW ATAN2 MIN MAX "
              "LT LE GT GE EQ NE AND OR WHERE").split()  # GD_EX_<name> = its position
 GD_EX_TO_COLUMN, GD_EX_TO_AUXW, GD_EX_TO_HOST_F64, GD_EX_TO_HOST_U8 = 0, 1, 2, 3
+# the table look-ups of gd_expr_eval_tab: op codes behind the GD_EX_ set, and its limits
+GD_TAB_OPS = {"INTERP": 34, "SPLINE1": 35, "SPLINE2": 36}  # GD_TAB_<name>
+GD_TAB_MAX_TABLES, GD_TAB_MAX_DOUBLES = 4, 1 << 22
+
+
+class GdExprTable(C.Structure):
+    """gd_expr_table of gdhip.h"""
+
+    _fields_ = [("kind", _i32), ("deriv", _i32), ("nx", _i32), ("ny", _i32), ("p0", _pd), ("p1", _pd), ("p2", _pd),
+                ("left", _f64), ("right", _f64)]
+
+
+def expr_table_structs(tables):
+    """The gd_expr_table array for the tables of a compiled expression (colexpr.Table objects, whose arrays it points
+    into: they must outlive the call it is passed to)."""
+    arr = (GdExprTable * len(tables))()
+    for t, st in zip(tables, arr):
+        st.kind, st.deriv, st.nx, st.ny = GD_TAB_OPS[t.kind], t.deriv, t.nx, t.ny
+        for name, a in zip(("p0", "p1", "p2"), t.arrays):
+            setattr(st, name, _dp(a))
+        st.left, st.right = t.left, t.right
+    return arr
 
 
 def format_field_bytes(width, prec):
@@ -789,12 +812,14 @@ class Context:
             raise ValueError("weights must have one entry per sample row")
         self._check(self.lib.gd_aux_weights(self.h, _dp(w)))
 
-    def expr_eval(self, code, consts, dst, dst_arg=0, lo=0, hi=None, stats=False):
+    def expr_eval(self, code, consts, dst, dst_arg=0, lo=0, hi=None, stats=False, tables=None):
         """Evaluate the postfix program ``code`` ((ncode, 2) int32 of (op, arg), constants ``consts``) over the rows [lo, hi)
         of the resident columns (gd_expr_eval).  ``dst``: GD_EX_TO_COLUMN (spare slot ``dst_arg``; returns the column index
         n + dst_arg), GD_EX_TO_AUXW (the auxiliary weight buffer receives sample weight * value; returns None),
         GD_EX_TO_HOST_F64 / GD_EX_TO_HOST_U8 (returns the hi - lo values as float64 / as bytes value != 0: views of
-        page-locked memory that the context recycles).  With ``stats`` the result is (that, [min, max, non-zero, NaNs])."""
+        page-locked memory that the context recycles).  With ``stats`` the result is (that, [min, max, non-zero, NaNs]).
+        ``tables``: the colexpr.Table objects the program's look-up ops refer to by slot (gd_expr_eval_tab); None or
+        empty for a program without."""
         code = np.ascontiguousarray(code, dtype=np.int32).reshape(-1, 2)
         consts = _f64arr(consts).ravel()
         hi = self.N if hi is None else int(hi)
@@ -802,8 +827,12 @@ class Context:
         if dst in (GD_EX_TO_HOST_F64, GD_EX_TO_HOST_U8):
             out = self.pinned_array((max(hi - int(lo), 0),), np.float64 if dst == GD_EX_TO_HOST_F64 else np.uint8)
         st = np.zeros(4) if stats else None
-        self._check(self.lib.gd_expr_eval(self.h, _ip(code), len(code), _dp(consts), consts.size, int(dst), int(dst_arg), int(lo),
-                                          hi, None if out is None else out.ctypes.data, None if st is None else _dp(st)))
+        args = (self.h, _ip(code), len(code), _dp(consts), consts.size, int(dst), int(dst_arg), int(lo), hi,
+                None if out is None else out.ctypes.data, None if st is None else _dp(st))
+        if tables:
+            self._check(self.lib.gd_expr_eval_tab(*args, expr_table_structs(tables), len(tables)))
+        else:
+            self._check(self.lib.gd_expr_eval(*args))
         res = self.n + int(dst_arg) if dst == GD_EX_TO_COLUMN else out
         return (res, st) if stats else res
 

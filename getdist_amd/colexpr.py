@@ -26,12 +26,17 @@ and ``m1 & m2`` for numpy's results.
 numpy's fast paths (x * x, sqrt, 1 / x, x) and are exact too, every other power is the device library's ``pow``, as are
 the other transcendental functions.  Division by zero and invalid operands give inf / NaN silently: numpy's
 RuntimeWarning is not reproduced (the device has no warning channel).
+
+Tabulated functions are nodes too (gd_expr_eval_tab): ``np.interp(expr, xp, fp, left, right)`` (or :func:`interp`),
+``Density1D.Prob(expr, derivative)`` and ``Density2D.Prob(ex, ey)`` of densities.py.  Their tables -- a :class:`Table`, held
+by the node and sent with every launch -- are host arrays; the values are numpy's ``np.interp``, this package's
+``Density1D.Prob`` of the host vector and scipy's ``RectBivariateSpline.ev`` bit for bit.
 """
 
 import numpy as np
 
 from ._lib import (GD_EX_MAX_CODE, GD_EX_MAX_COLS, GD_EX_MAX_CONST, GD_EX_MAX_STACK, GD_EX_OPS, GD_EX_TO_AUXW, GD_EX_TO_COLUMN,
-                   GD_EX_TO_HOST_F64, GD_EX_TO_HOST_U8, GD_EX_WEIGHT)
+                   GD_EX_TO_HOST_F64, GD_EX_TO_HOST_U8, GD_EX_WEIGHT, GD_TAB_MAX_DOUBLES, GD_TAB_MAX_TABLES, GD_TAB_OPS)
 
 OP = {name: k for k, name in enumerate(GD_EX_OPS)}
 
@@ -61,13 +66,49 @@ def _wrap(x):
     raise TypeError("unsupported operand for a column expression: %s" % type(x).__name__)
 
 
+class Table:
+    """The payload of a look-up node: ``kind`` ("INTERP", "SPLINE1" or "SPLINE2", an op of gd_expr_eval_tab), its host
+    ``arrays`` (float64, C-contiguous, read-only copies: knots and values / knots and interval coefficients / tx, ty, c),
+    the sizes ``nx`` and ``ny`` gd_expr_table wants, ``left`` / ``right`` of np.interp and the derivative order ``deriv`` of
+    a 1D spline.  Immutable; two nodes that hold the SAME Table object share one slot of a program."""
+
+    __slots__ = ("kind", "arrays", "nx", "ny", "left", "right", "deriv")
+
+    def __init__(self, kind, arrays, nx, ny=0, left=0.0, right=0.0, deriv=0):
+        frozen = []
+        for a in arrays:
+            a = np.array(a, dtype=np.float64, order="C", copy=True)
+            a.flags.writeable = False
+            frozen.append(a)
+        for k, v in zip(self.__slots__, (kind, tuple(frozen), int(nx), int(ny), float(left), float(right), int(deriv))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Table is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("Table is immutable")
+
+    def __reduce__(self):
+        return Table, (self.kind, self.arrays, self.nx, self.ny, self.left, self.right, self.deriv)
+
+    @property
+    def doubles(self):
+        return sum(a.size for a in self.arrays)
+
+    def __repr__(self):
+        shape = "%d" % self.nx if self.kind != "SPLINE2" else "%dx%d" % (self.nx - 4, self.ny - 4)
+        return "<%s table %s>" % (self.kind.lower(), shape)
+
+
 def _is_scalar(x):
     return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_))
 
 
 class ColumnExpr:
     """One node of an expression tree: ``kind`` is "col", "loglikes", "weights", "const", "pos" (promotion to float, no
-    instruction) or an op name of gd_expr_eval; ``args`` its operands; ``is_bool`` the type tracked on the host."""
+    instruction) or an op name of gd_expr_eval; ``args`` its operands; ``is_bool`` the type tracked on the host.  A look-up
+    node (kind "INTERP", "SPLINE1" or "SPLINE2", an op of gd_expr_eval_tab) holds its :class:`Table` behind its operands."""
 
     __slots__ = ("kind", "args", "is_bool")
     __array_priority__ = 1000
@@ -104,7 +145,7 @@ class ColumnExpr:
             return self.kind
         if self.kind == "const":
             return repr(self.args[0])
-        return "%s(%s)" % (self.kind.lower(), ", ".join(repr(a) for a in self.args))
+        return "%s(%s)" % (self.kind.lower(), ", ".join(repr(a) for a in self.args))  # (a Table names its kind and shape)
 
     # ---- node builders
     @staticmethod
@@ -187,6 +228,8 @@ class ColumnExpr:
             return where(*args)
         if func is np.clip:
             return _clip(*args, **kwargs)
+        if func is np.interp:
+            return interp(*args, **kwargs)
         raise TypeError("np.%s is not supported on column expressions" % getattr(func, "__name__", func))
 
     # ---- compilation and evaluation
@@ -198,8 +241,20 @@ class ColumnExpr:
         (op, arg), ``consts`` the float64 constants.  Names are resolved here (an unknown one raises ParamError); shared
         sub-trees are emitted once per use.  Raises ValueError when the program exceeds GD_EX_MAX_CODE instructions,
         GD_EX_MAX_STACK stack entries, GD_EX_MAX_CONST distinct constants or GD_EX_MAX_COLS distinct columns (the weights
-        and the loglikes count as columns)."""
-        code, consts, cols = [], {}, set()
+        and the loglikes count as columns) -- and for an expression with table look-ups, whose program is a triple: see
+        :meth:`compile_with_tables`."""
+        code, consts, tables = self.compile_with_tables(samples)
+        if tables:
+            raise ValueError("the expression holds %d table look-up(s) (np.interp, Density.Prob): its program comes with "
+                             "tables, use compile_with_tables(samples)" % len(tables))
+        return code, consts
+
+    def compile_with_tables(self, samples):
+        """(code, consts, tables): :meth:`compile` for any expression.  ``tables`` lists the distinct :class:`Table`
+        objects of the look-up nodes; the argument of a look-up op (_lib.GD_TAB_OPS) is its table's position there.  Also
+        raises ValueError for more than GD_TAB_MAX_TABLES distinct tables and for a table of more than GD_TAB_MAX_DOUBLES
+        doubles."""
+        code, consts, cols, tables = [], {}, set(), []
         depth = [0, 0]  # current, deepest
 
         def push():
@@ -222,6 +277,15 @@ class ColumnExpr:
                 push()
             elif k == "pos":
                 emit(node.args[0])
+            elif k in GD_TAB_OPS:  # args: the operands, then the Table
+                for a in node.args[:-1]:
+                    emit(a)
+                table = node.args[-1]
+                slot = next((i for i, t in enumerate(tables) if t is table), len(tables))
+                if slot == len(tables):
+                    tables.append(table)
+                code.append((GD_TAB_OPS[k], slot))
+                depth[0] -= len(node.args) - 2
             else:
                 for a in node.args:
                     emit(a)
@@ -237,8 +301,13 @@ class ColumnExpr:
             raise ValueError("the expression has %d distinct constants (at most %d)" % (len(consts), GD_EX_MAX_CONST))
         if len(cols) > GD_EX_MAX_COLS:
             raise ValueError("the expression reads %d distinct columns (at most %d)" % (len(cols), GD_EX_MAX_COLS))
+        if len(tables) > GD_TAB_MAX_TABLES:
+            raise ValueError("the expression refers to %d distinct tables (at most %d)" % (len(tables), GD_TAB_MAX_TABLES))
+        for t in tables:
+            if t.doubles > GD_TAB_MAX_DOUBLES:
+                raise ValueError("%r holds %d doubles (at most %d)" % (t, t.doubles, GD_TAB_MAX_DOUBLES))
         return (np.array(code, dtype=np.int32).reshape(-1, 2),
-                np.frombuffer(b"".join(consts), dtype=np.float64).copy() if consts else np.zeros(0))
+                np.frombuffer(b"".join(consts), dtype=np.float64).copy() if consts else np.zeros(0), tables)
 
     def _run(self, samples, dst, dst_arg=0):
         """Compile for ``samples``, make the loglikes resident when the expression reads them, and launch."""
@@ -247,11 +316,13 @@ class ColumnExpr:
         if getattr(samples, "_column_share", None) is not None:
             raise MCSamplesError("column expressions need every column resident on one device: this context holds only "
                                  "its rank's share of the columns (multi-GPU expressions are not supported)")
-        code, consts = self.compile(samples)
+        code, consts, tables = self.compile_with_tables(samples)
         if self.uses_loglikes():
             if samples.loglikes is None:
                 raise WeightedSampleError("Samples do not have logLikes (expression reads loglikes)")
             samples.ctx.set_extra_column(samples.ctx.EXTRA_COLS - 1, samples.loglikes)
+        if tables:
+            return samples.ctx.expr_eval(code, consts, dst, dst_arg, tables=tables)
         return samples.ctx.expr_eval(code, consts, dst, dst_arg)
 
     def eval(self, samples):
@@ -290,6 +361,31 @@ def where(c, a, b):
     """``a`` where ``c`` is non-zero, else ``b`` (np.where of three arguments); boolean when both branches are."""
     c, a, b = _wrap(c), _wrap(a), _wrap(b)
     return ColumnExpr("WHERE", (c, a, b), a.is_bool and b.is_bool)
+
+
+def lookup(kind, table, *operands):
+    """The float node that applies ``table`` (a :class:`Table` of that ``kind``) to its operand expression(s)."""
+    return ColumnExpr(kind, tuple(_wrap(a) for a in operands) + (table,), False)
+
+
+def interp(x, xp, fp, left=None, right=None, period=None):
+    """``np.interp(x, xp, fp, left, right)`` of the expression ``x``: numpy's values bit for bit (``left`` / ``right``,
+    NaN in gives NaN out, x equal to a knot gives its ``fp`` without arithmetic, repeated knots pick the last).  ``xp`` and
+    ``fp`` are 1-D host arrays of equal length >= 1, copied into the node.  Unlike numpy, which returns garbage there, an
+    ``xp`` that is not non-decreasing or holds a NaN or an infinity raises ValueError; ``period=`` is not supported."""
+    if period is not None:
+        raise TypeError("np.interp: period= is not supported on column expressions")
+    if isinstance(xp, ColumnExpr) or isinstance(fp, ColumnExpr):
+        raise TypeError("np.interp: xp and fp must be host arrays, only x can be a column expression")
+    if not isinstance(x, ColumnExpr):
+        raise TypeError("np.interp: x must be a column expression here (a host array cannot be mixed in)")
+    xp, fp = np.asarray(xp, dtype=np.float64), np.asarray(fp, dtype=np.float64)
+    if xp.ndim != 1 or fp.ndim != 1 or xp.size != fp.size or xp.size < 1:
+        raise ValueError("np.interp: xp and fp must be 1-D arrays of equal length >= 1")
+    if not np.all(np.isfinite(xp)) or np.any(xp[1:] < xp[:-1]):
+        raise ValueError("np.interp: xp must be finite and non-decreasing")
+    return lookup("INTERP", Table("INTERP", (xp, fp), xp.size, left=fp[0] if left is None else left,
+                                  right=fp[-1] if right is None else right), x)
 
 
 def _clip(a, a_min=None, a_max=None, **kwargs):

@@ -56,6 +56,12 @@ def getContourLevels(inbins, contours=defaultContours, missing_norm=0, half_edge
     return ranked[at] * (1 - back) + back * ranked[at - 1]
 
 
+def _is_expr(x):
+    from .colexpr import ColumnExpr
+
+    return isinstance(x, ColumnExpr)
+
+
 class NotAKnotSpline:
     """
     Cubic spline through (x_i, y_i) with the not-a-knot end condition (the third derivative is continuous at x_1 and
@@ -86,18 +92,40 @@ class NotAKnotSpline:
         ab[4, n - 3], ab[3, n - 2], ab[2, n - 1] = h[-1], -(h[-2] + h[-1]), h[-2]
         self.x, self.y, self.h, self.slope = x, y, h, slope
         self.M = solve_banded((2, 2), ab, rhs)
+        self._coef = None
+        self._tables = {}
+
+    def coefficients(self):
+        """(y, c1, c2, c3), each of length n - 1: on interval k, with t = x - x_k, the spline is
+        y[k] + t (c1[k] + t (c2[k] + t c3[k])).  Computed once; the host evaluation below and the device look-up
+        (:meth:`table`) read the same doubles."""
+        if self._coef is None:
+            h, M = self.h, self.M
+            c1 = self.slope - h * (2 * M[:-1] + M[1:]) / 6
+            c2 = M[:-1] / 2
+            c3 = (M[1:] - M[:-1]) / (6 * h)
+            self._coef = (self.y[:-1], c1, c2, c3)
+        return self._coef
+
+    def table(self, derivative=0):
+        """The colexpr.Table of this spline's ``derivative`` (0 .. 3) for a column expression: the knots and the
+        coefficients of :meth:`coefficients`, four per interval.  One object per derivative, so that uses share a slot."""
+        from .colexpr import Table
+
+        if derivative not in self._tables:
+            self._tables[derivative] = Table("SPLINE1", (self.x, np.stack(self.coefficients(), axis=1)), self.x.size,
+                                             deriv=derivative)
+        return self._tables[derivative]
 
     def __call__(self, xq, derivative=0, extrapolate=False):
         """Values (or derivatives) at ``xq``; beyond the end nodes zero, or the end cubic continued if ``extrapolate``."""
         xq = np.asarray(xq, dtype=float)
-        x, y, h, M = self.x, self.y, self.h, self.M
+        x = self.x
         k = np.clip(np.searchsorted(x, xq, side="right") - 1, 0, x.size - 2)
         t = xq - x[k]
-        c1 = self.slope[k] - h[k] * (2 * M[k] + M[k + 1]) / 6
-        c2 = M[k] / 2
-        c3 = (M[k + 1] - M[k]) / (6 * h[k])
+        y, c1, c2, c3 = (c[k] for c in self.coefficients())
         if derivative == 0:
-            out = y[k] + t * (c1 + t * (c2 + t * c3))
+            out = y + t * (c1 + t * (c2 + t * c3))
         elif derivative == 1:
             out = c1 + t * (2 * c2 + 3 * t * c3)
         elif derivative == 2:
@@ -195,9 +223,16 @@ class Density1D(GridDensity):
 
     def Prob(self, x, derivative=0):
         """Interpolated density (or its ``derivative``-th derivative) at ``x``: an array for sequences, a scalar for
-        a scalar; zero outside the grid."""
+        a scalar; zero outside the grid.  A column expression (colexpr.ColumnExpr) gives the expression of the density at
+        its values, evaluated on the device to the same doubles as the host vector would give here."""
         if self.spl is None:
             self._initSpline()
+        if _is_expr(x):
+            from .colexpr import ColumnExpr, lookup
+
+            if derivative not in (0, 1, 2, 3):  # as on the host: the fourth derivative of a cubic
+                return ColumnExpr("const", (0.0,), False)
+            return lookup("SPLINE1", self.spl.table(derivative), x)
         if isinstance(x, (np.ndarray, list, tuple)):
             return self.spl(x, derivative)
         return self.spl(np.array([x]), derivative)[0]
@@ -303,6 +338,7 @@ class Density2D(GridDensity):
         self.P
         state = dict(self.__dict__)
         state.pop("_wait", None)
+        state.pop("_coltab", None)
         state["spl"] = None
         return state
 
@@ -322,10 +358,31 @@ class Density2D(GridDensity):
     def __call__(self, *args, **kwargs):
         if self.spl is None:
             self._initSpline()
+        if any(_is_expr(a) for a in args) or any(_is_expr(a) for a in kwargs.values()):
+            return self._prob_expr(*args, **kwargs)
         return self.spl(*args, **kwargs)
 
+    def _prob_expr(self, x, y, grid=False, **kwargs):
+        """The column expression of the density at (x, y), each an expression or a Python scalar: the point evaluation
+        of the spline (scipy's ``ev``), run on the device from its knots and coefficients."""
+        from .colexpr import Table, lookup
+
+        if grid:
+            raise TypeError("Density2D.Prob of a column expression evaluates row by row: grid=True is not supported")
+        if kwargs:
+            raise TypeError("Density2D.Prob of a column expression does not take %s=" % ", ".join(sorted(kwargs)))
+        cached = self.__dict__.get("_coltab")  # (the spline it was made from, its Table): one Table per spline, so uses share a slot
+        if cached is None or cached[0] is not self.spl:
+            tx, ty, c = self.spl.tck
+            if tuple(self.spl.degrees) != (3, 3):
+                raise TypeError("only a bicubic spline can be applied to a column expression")
+            cached = self.__dict__["_coltab"] = (self.spl, Table("SPLINE2", (tx, ty, c), len(tx), len(ty)))
+        return lookup("SPLINE2", cached[1], x, y)
+
     def Prob(self, x, y, grid=False):
-        """Interpolated density at the points (x, y), or on their outer product with ``grid=True``."""
+        """Interpolated density at the points (x, y), or on their outer product with ``grid=True``.  With a column
+        expression (colexpr.ColumnExpr) for x, y or both -- the other may be a number -- the expression of the density at
+        those points (not with ``grid=True``)."""
         return self(x, y, grid=grid)
 
 

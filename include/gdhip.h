@@ -666,6 +666,47 @@ int gd_parse_rows(gd_ctx* ctx, const void* d_text, int64_t nbytes, int32_t last,
 int gd_expr_eval(gd_ctx* ctx, const int32_t* code, int32_t ncode, const double* consts, int32_t nconst, int32_t dst,
                  int32_t dst_arg, int64_t lo, int64_t hi, void* host_out, double* stats_out);
 
+/* gd_expr_eval_tab: gd_expr_eval with table look-ups -- np.interp(expr, xp, fp), Density1D.Prob(expr) and
+ * Density2D.Prob(ex, ey) of colexpr.py.  Same arguments, destinations, tallies and errors, plus `ntab` tables of host
+ * doubles and three more ops whose argument is the table slot (their codes and these limits are NOT part of the GD_EX_
+ * set: gd_expr_eval keeps refusing them as unknown ops):
+ *   GD_TAB_INTERP   pops x, pushes np.interp(x, p0, p1, left, right): p0 = the nx knots (non-decreasing), p1 = the nx
+ *                   values.  numpy's arr_interp step for step: NaN gives NaN (nx == 1: p1[0], as numpy does), x below
+ *                   / above the knots gives left / right, the interval is the largest j with p0[j] <= x, x equal to a
+ *                   knot (and the last knot) gives p1[j] without arithmetic, else slope * (x - p0[j]) + p1[j] with
+ *                   numpy's retry from the right-hand knot when that is NaN.
+ *   GD_TAB_SPLINE1  pops x, pushes derivative `deriv` (0 .. 3) of the piecewise cubic with the nx knots p0 and the
+ *                   4 (nx - 1) coefficients p1 = {y, c1, c2, c3} per interval: with k = the interval of x and
+ *                   t = x - p0[k], y + t (c1 + t (c2 + t c3)); 0.0 outside [p0[0], p0[nx - 1]], NaN for NaN
+ *                   (densities.NotAKnotSpline, whose host evaluation is the same expression).
+ *   GD_TAB_SPLINE2  pops y, then x, pushes the bicubic tensor-product B-spline with knots p0 (nx of them), p1 (ny) and
+ *                   the (nx - 4) (ny - 4) coefficients p2 at (x, y), as FITPACK's fpbisp evaluates one point
+ *                   (scipy's RectBivariateSpline.ev): arguments clamped to the knot range, fpbspl's recursion with its
+ *                   equal-knot guard, the 16 terms summed as sp = sp + (c hx) hy in fpbisp's loop order.
+ * Nothing is contracted into an fma, so all three equal numpy / scipy bit for bit.  `kind` of a table is the op that
+ * may refer to it.  The tables are copied into the context's scratch on its stream ahead of the launch and are not kept.
+ * GD_ERR_BADARG before any launch, in addition to gd_expr_eval's: ntab outside 0 .. GD_TAB_MAX_TABLES, tables NULL with
+ * ntab > 0, a table slot out of range, a table whose kind is not the op's, a null table pointer, nx < 1 (INTERP), nx < 4
+ * (SPLINE1), nx or ny < 8 (SPLINE2), a table of more than GD_TAB_MAX_DOUBLES doubles in all, deriv outside 0 .. 3, knots
+ * that are not finite or not non-decreasing.  With ntab == 0 the call IS gd_expr_eval: the same kernel runs. */
+#define GD_TAB_INTERP 34
+#define GD_TAB_SPLINE1 35
+#define GD_TAB_SPLINE2 36
+#define GD_TAB_MAX_TABLES 4
+#define GD_TAB_MAX_DOUBLES 4194304
+typedef struct gd_expr_table {
+    int32_t kind;  /* GD_TAB_INTERP / GD_TAB_SPLINE1 / GD_TAB_SPLINE2 */
+    int32_t deriv; /* SPLINE1: the derivative order; else 0 */
+    int32_t nx, ny;
+    const double* p0; /* host pointers, see above; unused ones may be NULL */
+    const double* p1;
+    const double* p2;
+    double left, right; /* INTERP: the values below p0[0] / above p0[nx - 1] */
+} gd_expr_table;
+int gd_expr_eval_tab(gd_ctx* ctx, const int32_t* code, int32_t ncode, const double* consts, int32_t nconst, int32_t dst,
+                     int32_t dst_arg, int64_t lo, int64_t hi, void* host_out, double* stats_out, const gd_expr_table* tables,
+                     int32_t ntab);
+
 /* ---------------------------------------------------------------- stand-alone convolutions -------
  * The device-backed forms of getdist/convolve.py's public functions (host arrays in and out; the Python module
  * getdist_amd/convolve.py does the padding, the centring roll and the mode slices exactly as convolve.py:196-444).
