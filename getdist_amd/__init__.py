@@ -17,7 +17,7 @@ _EXPORTS = {
     "covToCorr": "chains", "Density1D": "densities", "Density2D": "densities", "DensityND": "densities", "GridDensity": "densities",
     "DensitiesError": "densities", "getContourLevels": "densities", "nearestFFTnumber": "convolve",
     "loadMCSamples": "chainfiles", "chainFiles": "chainfiles", "prefill_plot_caches": "plotting",
-    "ColumnExpr": "colexpr",
+    "ColumnExpr": "colexpr", "ContourPaths": "contourpaths", "contour_paths": "contourpaths",
 }
 
 

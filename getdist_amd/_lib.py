@@ -112,6 +112,8 @@ SIGNATURES = {
     "gd_clone_samples": (C.c_int, [_p, _p]),
     "gd_bind_thread": (C.c_int, [_p]),
     "gd_contour_levels": (C.c_int, [_p, _i32, _i32, _p, _pd, _i32, _pd, _pi32]),
+    "gd_contour_paths": (C.c_int, [_p, _i32, _p, _pi64, _pi32, _pi32, _pd, _pi64, _i64, _pd, _pi64, _i64, _pd, _i32, _p, _p, _pi64,
+                                   _pi64, _pi32]),
     "gd_limits1d": (C.c_int, [_p, _i32, _i32, _pd, _pd, _pd, _pd, _i32, _i32, _pd, _pi32]),
     "gd_set_extra_column": (C.c_int, [_p, _i32, _pd]),
     "gd_aux_weights": (C.c_int, [_p, _pd]),
@@ -179,6 +181,8 @@ GD_EX_TO_COLUMN, GD_EX_TO_AUXW, GD_EX_TO_HOST_F64, GD_EX_TO_HOST_U8 = 0, 1, 2, 3
 # the table look-ups of gd_expr_eval_tab: op codes behind the GD_EX_ set, and its limits
 GD_TAB_OPS = {"INTERP": 34, "SPLINE1": 35, "SPLINE2": 36}  # GD_TAB_<name>
 GD_TAB_MAX_TABLES, GD_TAB_MAX_DOUBLES = 4, 1 << 22
+GD_PATHS_XY, GD_PATHS_FLAG, GD_PATHS_LOOPS = 0, 1, 2
+PATHS_ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, _i32, _i64)  # gd_paths_alloc_fn
 
 
 class GdExprTable(C.Structure):
@@ -852,6 +856,56 @@ class Context:
         self._check(self.lib.gd_contour_levels(self.h, int(B), int(F), d_P.ptr, _dp(contours), len(contours), _dp(out),
                                                _ip(status)))
         return out, status
+
+    # ---- contour paths
+    def contour_paths(self, d_grids, grid_off, ny, nx, x_axes, x_off, y_axes, y_off, levels):
+        """gd_contour_paths over B grids at ``d_grids`` (a device buffer or address; grid b is ny[b] x nx[b] doubles from element
+        grid_off[b] on), its axes the nx[b] entries of ``x_axes`` from x_off[b] on and the ny[b] of ``y_axes`` from y_off[b] on
+        (grids may share an axis), and ``levels`` (B, nc).  Returns (xy (V, 2)
+        float64, flag (V) uint8, loops (L) int32, task_vert_off (B*nc + 1) int64, task_loop_off (B*nc + 1) int64, status (B)
+        int32): task b*nc + c owns the vertices [task_vert_off[t], task_vert_off[t+1]) and the loops
+        [task_loop_off[t], task_loop_off[t+1]), ``loops`` holding each loop's first vertex relative to its task's;
+        status[b] != 0 marks a grid with a non-finite value (then nothing was traced).  Results above 1 MB are views of
+        page-locked memory that the context recycles once they are released."""
+        grid_off = np.ascontiguousarray(grid_off, dtype=np.int64)
+        ny, nx, x_axes, y_axes = _i32arr(ny), _i32arr(nx), _f64arr(x_axes).reshape(-1), _f64arr(y_axes).reshape(-1)
+        x_off, y_off = np.ascontiguousarray(x_off, dtype=np.int64), np.ascontiguousarray(y_off, dtype=np.int64)
+        levels = _f64arr(levels)
+        B = len(ny)
+        if levels.ndim != 2 or levels.shape[0] != B or not (len(nx) == len(grid_off) == len(x_off) == len(y_off) == B):
+            raise ValueError("contour_paths: one size, one grid offset, two axis offsets and one row of levels per grid")
+        nc = levels.shape[1]
+        T = B * nc
+        voff, loff = np.zeros(T + 1, dtype=np.int64), np.zeros(T + 1, dtype=np.int64)
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        kinds = {GD_PATHS_XY: (np.float64, 2), GD_PATHS_FLAG: (np.uint8, 1), GD_PATHS_LOOPS: (np.int32, 1)}
+        got = {}
+
+        def alloc(user, which, count):
+            try:  # (never let an exception unwind through the C frames)
+                dtype, per = kinds[which]
+                n = int(count) * per
+                if n * np.dtype(dtype).itemsize > (1 << 20):
+                    a = self.pinned_array((n,), dtype)
+                else:
+                    a = np.empty(max(n, 1), dtype=dtype)[:n]
+                got[which] = a
+                return a.ctypes.data
+            except Exception:
+                return None
+
+        cb = PATHS_ALLOC_FN(alloc)
+        ptr = d_grids.ptr if isinstance(d_grids, DevBuf) else d_grids
+        self._check(self.lib.gd_contour_paths(self.h, B, ptr, grid_off.ctypes.data_as(_pi64), _ip(ny), _ip(nx), _dp(x_axes),
+                                              x_off.ctypes.data_as(_pi64), x_axes.size, _dp(y_axes),
+                                              y_off.ctypes.data_as(_pi64), y_axes.size, _dp(levels), nc, C.cast(cb, _p), None, voff.ctypes.data_as(_pi64),
+                                              loff.ctypes.data_as(_pi64), _ip(status)))
+        # (pop: the callback object and its closure form a cycle that only the collector frees; what it still held would
+        # keep the page-locked blocks from being recycled until then)
+        xy = got.pop(GD_PATHS_XY, np.zeros(0)).reshape(-1, 2)
+        flag = got.pop(GD_PATHS_FLAG, np.zeros(0, dtype=np.uint8))
+        loops = got.pop(GD_PATHS_LOOPS, np.zeros(0, dtype=np.int32))
+        return xy, flag, loops, voff, loff, status[:B]
 
     def density2d_enqueue(self, d_hist, B, F, rx, ry, corr, winw, flags, bco, mbc, status):
         """density2d without the final wait: ``status`` is a page-locked int32 array of length B (pinned_array) that is

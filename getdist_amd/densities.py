@@ -385,6 +385,14 @@ class Density2D(GridDensity):
         those points (not with ``grid=True``)."""
         return self(x, y, grid=grid)
 
+    def getContourPaths(self, levels=None, ctx=None):
+        """The contour geometry of this density, traced on the device (contourpaths.contour_paths of this one grid, which
+        need not be square): a ContourPaths at ``levels`` (default: ``self.contours``; DensitiesError when those are not
+        set).  ``ctx``: the device context, None opens Context(0) for the call."""
+        from .contourpaths import contour_paths
+
+        return contour_paths([self], levels=levels, ctx=ctx)[0]
+
 
 class DensityND(GridDensity):
     """

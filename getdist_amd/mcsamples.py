@@ -2098,6 +2098,19 @@ class MCSamples(Chains):
             return route(self, pairs, num_plot_contours, get_density, _bandwidths, meanlikes, mask_function=mask_function,
                          **kwargs)
 
+    def get2DContourPaths(self, pairs, num_plot_contours=None, meanlikes=False, **kwargs):
+        """
+        Batched 2D contour geometry (additive API): one contourpaths.ContourPaths per (x, y) entry of ``pairs``, at the
+        contour levels of ``self.contours`` (the first ``num_plot_contours`` of them).  The densities come from
+        ``get2DDensities(..., get_density=False)`` with the same keyword arguments and stay attached as ``.density``; their
+        grids are traced on this sample set's device in one native call (gd_contour_paths).
+        """
+        from .contourpaths import contour_paths
+
+        densities = self.get2DDensities(pairs, num_plot_contours=num_plot_contours, get_density=False, meanlikes=meanlikes,
+                                        **kwargs)
+        return contour_paths(densities, ctx=self.ctx)
+
     # ---- the optional branches of the native route -------------------------------------------------------------------
     def _pair_neff_2d(self, pa):
         """use_effective_samples_2D (mcsamples.py:1322-1328): the 2D estimate per pair, the smaller 1D one for a pair that is

@@ -335,6 +335,44 @@ int gd_bind_thread(gd_ctx* ctx);
 int gd_contour_levels(gd_ctx* ctx, int32_t B, int32_t F, const void* d_P, const double* contours, int32_t nc, double* out,
                       int32_t* status_out);
 
+/* ---------------------------------------------------------------- contour paths ----------------
+ * gd_contour_paths: the contour geometry of B grids at nc levels each (1..8), what a plotter otherwise gets from a
+ *   host contouring library grid by grid.  Grid b is ny[b] x nx[b] doubles (sides 2..4096, row-major, P[iy][ix]) at
+ *   d_grids + grid_off[b] (device, offsets in doubles); its axes are the nx[b] entries of x_axes from x_off[b] on and the
+ *   ny[b] of y_axes from y_off[b] on (host arrays of x_count / y_count doubles, increasing, used as given; grids may share
+ *   an axis -- the pairs of a triangle do); its levels are levels[b*nc ..].  Task t = b*nc + c is (grid b, level c).
+ * Semantics per task: a node is above iff P > level (a node at the level is below).  One ring of virtual nodes that
+ *   are always below surrounds the grid, at the positions of the edge nodes, so the result is the boundary of
+ *   {P > level} as closed loops that run along the domain edge where the set touches it.  Edges of the padded
+ *   (ny+2) x (nx+2) lattice are numbered: horizontal (j,i)-(j,i+1) is j*(nx+1)+i, vertical (j,i)-(j+1,i) is
+ *   (ny+2)*(nx+1) + j*(nx+2)+i.  A crossed edge (exactly one end above) between real nodes a (lower index) and b
+ *   carries the vertex pa*(1-f) + pb*f, f = (level - za)/(zb - za), on the varying coordinate (no fused multiply-add);
+ *   a crossed edge to the ring carries the real node's own position with flag 1 ("on the domain boundary").  Walking
+ *   a cell's corners counter-clockwise -- (j,i), (j,i+1), (j+1,i+1), (j+1,i) -- a segment starts on the edge where the
+ *   walk goes above -> below and ends where it goes below -> above: the above side is on the left, peaks run
+ *   counter-clockwise and holes clockwise.  In a saddle cell the centre is above iff all four corners are real and
+ *   0.25*(z0+z1+z2+z3) > level; then a start on edge k ends on edge k+1, otherwise on edge k-1.  Loops are listed by
+ *   increasing smallest edge id, each from that edge on in segment direction.  A grid entirely above gives one loop,
+ *   the domain rectangle (all flagged); a grid entirely below gives none.
+ * Results (host): task_vert_off[T+1] and task_loop_off[T+1] (T = B*nc) are the offsets of every task in the vertex
+ *   and loop arrays, which the call asks `alloc(user, which, count)` for once their sizes are known -- GD_PATHS_XY:
+ *   count x 2 doubles, GD_PATHS_FLAG: count bytes, GD_PATHS_LOOPS: count int32, the first vertex of every loop relative
+ *   to its task's first vertex.  `alloc` returns the storage (page-locked for a fast copy) or NULL to fail the call with
+ *   GD_ERR_NOMEM; it is not called when there is no vertex at all.  status_out[b] != 0: grid b holds a non-finite value;
+ *   then nothing is traced, all offsets are 0 and the call still returns GD_OK.
+ * One workgroup per task: a count pass, a device scan of the counts (only the totals come back: results and scratch
+ *   are sized exactly), then compaction of the crossed edges in id order and ordering of the cycles by pointer jumping
+ *   (csrc/contourpaths.hip).  GD_ERR_BADARG before any launch for nc outside 1..8, a side outside 2..4096, an axis
+ *   offset outside its array, a non-finite level.  Blocks until the results are complete. */
+#define GD_PATHS_XY 0
+#define GD_PATHS_FLAG 1
+#define GD_PATHS_LOOPS 2
+typedef void* (*gd_paths_alloc_fn)(void* user, int32_t which, int64_t count);
+int gd_contour_paths(gd_ctx* ctx, int32_t B, const void* d_grids, const int64_t* grid_off, const int32_t* ny, const int32_t* nx,
+                     const double* x_axes, const int64_t* x_off, int64_t x_count, const double* y_axes, const int64_t* y_off,
+                     int64_t y_count, const double* levels, int32_t nc, gd_paths_alloc_fn alloc, void* user,
+                     int64_t* task_vert_off, int64_t* task_loop_off, int32_t* status_out);
+
 /* ---------------------------------------------------------------- credible limits 1D -----------
  * gd_limits1d: densities.py:186-248 Density1D.initLimitGrids + getLimits for B densities on regular grids
  *   (host arrays: P is B x F, x0[b] the first grid abscissa, spacing[b] the grid step).  Each density is refined
