@@ -162,6 +162,10 @@ SIGNATURES = {
     "gd_parse_rows": (C.c_int, [_p, _p, _i64, _i32, _i64, _i32, _p, _i64, _i64, _p, _i64, _pi64]),
     "gd_expr_eval": (C.c_int, [_p, _pi32, _i32, _pd, _i32, _i32, _i32, _i64, _i64, _p, _pd]),
     "gd_expr_eval_tab": (C.c_int, [_p, _pi32, _i32, _pd, _i32, _i32, _i32, _i64, _i64, _p, _pd, _p, _i32]),
+    "gd_upload_device": (C.c_int, [_p, _p, _i32, _i32, _i32, _pi32, _i32, C.POINTER(_p), _i32]),
+    "gd_pointer_info": (C.c_int, [_p, _p, _pi32, _pi32]),
+    "gd_fetch_device_array": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p, _pd]),
+    "gd_download_samples": (C.c_int, [_p, _pd]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
@@ -172,6 +176,10 @@ GD_FORMAT_MORE_BYTES = -22
 GD_FMT_SRC_WEIGHT, GD_FMT_SRC_ZERO, GD_FMT_SRC_ONE = -1, -2, -3
 GD_FMT_MAX_PREC, GD_FMT_MAX_WIDTH = 17, 32
 GD_PARSE_NOT_PLAIN = -23
+# gd_upload_device / gd_fetch_device_array: a valid description the call does not serve -- memory the host can read as well
+# (page-locked, managed) or negative strides; device memory of another device; a pointer the runtime does not know
+GD_ERR_DECLINED, GD_ERR_OTHER_DEVICE, GD_ERR_NOT_DEVICE = -24, -25, -26
+GD_PTR_DEVICE, GD_PTR_PINNED, GD_PTR_MANAGED, GD_PTR_UNKNOWN = 0, 1, 2, 3
 GD_PARSE_MAX_LINE = 8192
 GD_EX_MAX_CODE, GD_EX_MAX_STACK, GD_EX_MAX_CONST, GD_EX_MAX_COLS = 128, 16, 32, 16
 GD_EX_WEIGHT = -1
@@ -223,6 +231,13 @@ def skipped_text_bytes(f, skiprows):
             return None
         start += len(line)
     return start
+
+
+class GdDevPart(C.Structure):
+    """gd_dev_part of gdhip.h"""
+
+    _fields_ = [("base", _p), ("rows", _i64), ("cols", _i64), ("row_stride", _i64), ("col_stride", _i64), ("weights", _p),
+                ("w_stride", _i64)]
 
 
 _lib = None
@@ -514,6 +529,91 @@ class Context:
         self._check(self.lib.gd_upload(self.h, s.ctypes.data, N, n, rs, cs, None if w is None else w.ctypes.data))
         self._keep = None
         self.N, self.n, self.weighted = N, n, w is not None
+
+    def upload_device(self, parts, weights=None, keep=None):
+        """A sample set of this context's own from device arrays (gd_upload_device).  ``parts``: one 2-D devarray.DevArray per
+        chain, of one element type and column count; ``weights``: None or one 1-D DevArray per part, of one element type;
+        ``keep``: the source columns to keep (None: all).  The context's stream is ordered behind the arrays' producer
+        streams (events, no host wait); the source is copied, never adopted.  False when the library declines (page-locked or
+        managed memory, negative strides): the caller takes the host route and the previous set is still resident.
+        ValueError for memory of another device."""
+        arr = (GdDevPart * len(parts))()
+        for k, (st, d) in enumerate(zip(arr, parts)):
+            st.base, (st.rows, st.cols), (st.row_stride, st.col_stride) = d.ptr or None, d.shape, d.strides
+            if weights is not None:
+                st.weights, st.w_stride = weights[k].ptr or None, weights[k].strides[0]
+        everything = list(parts) + list(weights or [])
+        streams = []
+        for d in everything:
+            if d.stream is not None and d.shape[0] and d.stream not in streams:
+                streams.append(d.stream)
+        handles = (_p * max(len(streams), 1))(*streams)
+        keep = None if keep is None else _i32arr(keep)
+        rc = self.lib.gd_upload_device(self.h, arr, len(parts), int(parts[0].dtype), int(weights[0].dtype) if weights else 0,
+                                       None if keep is None else _ip(keep), 0 if keep is None else len(keep), handles, len(streams))
+        if not self._served(rc, everything):
+            return False
+        self.N = int(sum(d.shape[0] for d in parts))
+        self.n, self.weighted = int(parts[0].shape[1] if keep is None else len(keep)), weights is not None
+        return True
+
+    def pointer_info(self, ptr):
+        """(GD_PTR_* kind, device index or -1) of a pointer, as the runtime sees it (gd_pointer_info)"""
+        kind, dev = C.c_int32(), C.c_int32()
+        self._check(self.lib.gd_pointer_info(self.h, int(ptr), C.byref(kind), C.byref(dev)))
+        return int(kind.value), int(dev.value)
+
+    def _served(self, rc, arrays):
+        """True for success, False for GD_ERR_DECLINED (memory the host can read as well, or negative strides: the caller takes
+        the host route).  Device memory of another device is a ValueError that names the device to pass; anything else
+        raises as usual (a pointer the runtime does not know included)."""
+        if rc == GD_ERR_DECLINED:
+            return False
+        if rc == GD_ERR_OTHER_DEVICE:
+            for d in arrays:
+                kind, dev = self.pointer_info(d.ptr) if d.ptr else (GD_PTR_UNKNOWN, -1)
+                if kind == GD_PTR_DEVICE and dev != self.device:
+                    raise ValueError("the array lives on device %d: pass device=%d" % (dev, dev))
+        self._check(rc)
+        return True
+
+    def fetch_device_array(self, desc):
+        """The 1-D or 2-D devarray.DevArray as a float64 host array (gd_fetch_device_array), negative strides included; None
+        when the library declines the memory."""
+        fwd, flipped = desc.forward()
+        d2 = fwd.as2d()
+        out = np.empty(d2.shape)
+        if out.size:
+            rc = self.lib.gd_fetch_device_array(self.h, d2.ptr, d2.shape[0], d2.shape[1], d2.strides[0], d2.strides[1],
+                                                int(d2.dtype), d2.stream, _dp(out))
+            if not self._served(rc, [d2]):
+                return None
+        out = out.reshape(desc.shape)
+        for ax in flipped:
+            out = np.flip(out, ax)
+        return out
+
+    def download_samples(self):
+        """The resident columns as an (N, n) row-major float64 array in page-locked memory (gd_download_samples)."""
+        out = self.pinned_array((self.N, self.n))
+        self._check(self.lib.gd_download_samples(self.h, _dp(out)))
+        return out
+
+    def read_row(self, i):
+        """Row ``i`` of the resident columns (n values) by one gather of 16-byte items (gd_gather_items): the pair of
+        rows that holds it, per column."""
+        import types
+
+        ld, i = (self.N + 511) // 512 * 512, int(i)
+        if self.n * ld // 2 >= 1 << 31:
+            raise ValueError("row read: the resident set is too large for 32-bit item indices")
+        src = types.SimpleNamespace(ptr=self.column_ptr(0))
+        dst = self.alloc(self.n * 16)
+        try:
+            self.gather_items(dst, src, (np.arange(self.n, dtype=np.int64) * ld + i) // 2, 16)
+            return dst.to_host((self.n, 2))[:, i & 1].copy()
+        finally:
+            dst.free()
 
     def upload_shard(self, cols_f, N, n, col_first, weights=None):
         """This rank's block of columns only (``cols_f``: (N, count) Fortran-ordered fp64, the columns

@@ -126,6 +126,31 @@ class WeightedSamples:
     private helpers they share.
     """
 
+    # ---- the host mirror of the samples ----------------------------------------------------------------------
+    # ``samples`` is the reference's (N, n) fp64 host array.  A set built from host data stores it at construction and never
+    # downloads anything; a set built from a device array (MCSamples._read_device_chains) has none until it is first read:
+    # then the resident columns are downloaded once (gd_download_samples) and kept.
+    @property
+    def samples(self):
+        s = self.__dict__.get("_samples")
+        if s is None and self.__dict__.get("_samples_on_device"):
+            s = self.__dict__["_samples"] = self.ctx.download_samples()
+        return s
+
+    @samples.setter
+    def samples(self, value):
+        self.__dict__["_samples"] = value
+        self.__dict__["_samples_on_device"] = False
+
+    @property
+    def _host_mirror_ready(self):
+        """False while the samples of a set built from a device array exist on the device only"""
+        return self.__dict__.get("_samples") is not None
+
+    def _sample_row(self, i):
+        """samples[i] without forming the host mirror for it"""
+        return self.samples[i] if self._host_mirror_ready else self.ctx.read_row(i)
+
     # ---- replacing the sample set (chains.py:276-323) --------------------------------------------------------
     def setSamples(self, samples, weights=None, loglikes=None, min_weight_ratio=None):
         """chains.py:276-300: replace samples / weights; drops the device mirror and every derived cache."""

@@ -517,6 +517,36 @@ int gd_gather_items(gd_ctx* ctx, void* d_dst, const void* d_src, const int32_t* 
     return GD_OK;
 }
 
+// What an upload derives from the resident weight column `w` (N values, already enqueued on the stream): the integral flag,
+// the total (added in a fixed order) and, for multiplicities up to 255, the byte copy.  Shared by the host and the device
+// route (gd_upload, gd_upload_device).
+static int upload_weight_flags(gd_ctx* ctx, const double* w, int64_t N, int64_t ld, unsigned char** w8_out, bool* integral_out,
+                               double* wsum_out) {
+    unsigned char*& w8 = *w8_out;
+    constexpr int WSLOTS = 1024 * 4;
+    char* chk = (char*)gd_scratch(ctx, 128 + WSLOTS * 8);
+    if (!chk) return GD_ERR_NOMEM;
+    GD_HIP(hipMemsetAsync(chk, 0, 128, ctx->stream));
+    k_weights_integral<<<1024, 256, 0, ctx->stream>>>(w, N, (int*)chk, (double*)(chk + 128));
+    GD_KERNEL_CHECK();
+    int bad = 1;
+    double sum = 0;
+    std::vector<double> slots(WSLOTS);
+    GD_TRY(gd_fetch(ctx, &bad, chk, 4));
+    GD_TRY(gd_fetch(ctx, slots.data(), chk + 128, (size_t)WSLOTS * 8));
+    GD_TRY(gd_stream_sync(ctx));
+    for (double v : slots) sum += v;
+    *wsum_out = (bad & 4) ? 0.0 : sum;
+    *integral_out = ((bad & 1) == 0) && sum < 4.0e9;
+    if (*integral_out && bad == 0) {  // byte multiplicities for the 16-bit packed 2D binning
+        GD_HIP(hipMalloc((void**)&w8, (size_t)ld));
+        GD_HIP(hipMemsetAsync(w8, 0, (size_t)ld, ctx->stream));
+        k_weights_to_u8<<<1024, 256, 0, ctx->stream>>>(w, N, w8);
+        GD_KERNEL_CHECK();
+    }
+    return GD_OK;
+}
+
 // Builds the new sample set in locals; the context is only touched once everything has succeeded, so a failed upload
 // leaves it EMPTY (cols == nullptr, N == 0), never half-initialised.
 // shard_first >= 0: X holds only the columns [shard_first, shard_first + shard_count) of the n (column-major); the others
@@ -561,27 +591,7 @@ static int upload_build(gd_ctx* ctx, const double* X, int64_t N, int64_t n, int6
     if (weights) {
         GD_HIP(hipMalloc((void**)&w, (size_t)(ld * 8)));
         GD_HIP(hipMemcpyAsync(w, weights, (size_t)(N * 8), hipMemcpyHostToDevice, ctx->stream));
-        constexpr int WSLOTS = 1024 * 4;
-        char* chk = (char*)gd_scratch(ctx, 128 + WSLOTS * 8);
-        if (!chk) return GD_ERR_NOMEM;
-        GD_HIP(hipMemsetAsync(chk, 0, 128, ctx->stream));
-        k_weights_integral<<<1024, 256, 0, ctx->stream>>>(w, N, (int*)chk, (double*)(chk + 128));
-        GD_KERNEL_CHECK();
-        int bad = 1;
-        double sum = 0;
-        std::vector<double> slots(WSLOTS);
-        GD_TRY(gd_fetch(ctx, &bad, chk, 4));
-        GD_TRY(gd_fetch(ctx, slots.data(), chk + 128, (size_t)WSLOTS * 8));
-        GD_TRY(gd_stream_sync(ctx));
-        for (double v : slots) sum += v;
-        *wsum_out = (bad & 4) ? 0.0 : sum;
-        *integral_out = ((bad & 1) == 0) && sum < 4.0e9;
-        if (*integral_out && bad == 0) {  // byte multiplicities for the 16-bit packed 2D binning
-            GD_HIP(hipMalloc((void**)&w8, (size_t)ld));
-            GD_HIP(hipMemsetAsync(w8, 0, (size_t)ld, ctx->stream));
-            k_weights_to_u8<<<1024, 256, 0, ctx->stream>>>(w, N, w8);
-            GD_KERNEL_CHECK();
-        }
+        GD_TRY(upload_weight_flags(ctx, w, N, ld, w8_out, integral_out, wsum_out));
     }
     GD_TRY(gd_stream_sync(ctx));
     return GD_OK;
@@ -883,3 +893,14 @@ int gd_attach_samples(gd_ctx* ctx, gd_ctx* owner) {
 }
 
 }  // extern "C"
+
+// The same three steps for devinput.hip (gd_upload_device installs a sample set through the ends every other way uses).
+int gd_upload_release(gd_ctx* ctx) { return upload_release(ctx); }
+void gd_upload_install(gd_ctx* ctx, double* cols, double* w, unsigned char* w8, bool integral, double wsum, int64_t N, int64_t n,
+                       int64_t ld) {
+    upload_install(ctx, cols, w, w8, integral, wsum, N, n, ld);
+}
+int gd_upload_weight_flags(gd_ctx* ctx, const double* w, int64_t N, int64_t ld, unsigned char** w8_out, bool* integral_out,
+                           double* wsum_out) {
+    return upload_weight_flags(ctx, w, N, ld, w8_out, integral_out, wsum_out);
+}

@@ -140,6 +140,14 @@ int gd_fetch(gd_ctx* ctx, void* host_dst, const void* d_src, size_t bytes);
 int gd_fetch_pinned(gd_ctx* ctx, void* pinned_dst, const void* d_src, size_t bytes);
 int gd_stream_sync(gd_ctx* ctx);
 
+// core.hip: the two ends of installing a sample set (release leaves the context EMPTY, install hands it the finished
+// allocations) and what an upload derives from the resident weight column, for gd_upload_device (devinput.hip)
+int gd_upload_release(gd_ctx* ctx);
+void gd_upload_install(gd_ctx* ctx, double* cols, double* w, unsigned char* w8, bool integral, double wsum, int64_t N, int64_t n,
+                       int64_t ld);
+int gd_upload_weight_flags(gd_ctx* ctx, const double* w, int64_t N, int64_t ld, unsigned char** w8_out, bool* integral_out,
+                           double* wsum_out);
+
 int gd_fail(gd_ctx* ctx, int code, const char* fmt, ...);
 void gd_comm_release(gd_ctx* ctx);  // comm.hip
 bool gd_ctx_alive(gd_ctx* ctx);

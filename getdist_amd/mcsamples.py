@@ -316,10 +316,20 @@ class MCSamples(Chains):
         else:
             for nm, rng in (ranges or {}).items():
                 self.ranges.setRange(nm, rng)
-        samples, weights, loglikes, fixed = self._read_chains(samples, weights, loglikes, ignore_lines)
-        self.samples = samples
+        self._device_installed = False
+        on_device = self._read_device_chains(samples, weights, loglikes, ignore_lines, device, _context_factory or Context)
+        if isinstance(on_device, dict):  # the columns are resident already; the host mirror is made when first read
+            weights, loglikes, fixed = on_device["weights"], on_device["loglikes"], on_device["fixed"]
+            self._samples, self._samples_on_device = None, True
+            self.numrows, n_kept = on_device["numrows"], on_device["n"]
+        else:
+            if on_device is not None:  # device arrays the device route does not serve, as host arrays
+                samples, weights, loglikes = on_device
+            samples, weights, loglikes, fixed = self._read_chains(samples, weights, loglikes, ignore_lines)
+            self.samples = samples
+            self.numrows, n_kept = samples.shape
         self.loglikes = loglikes
-        self.numrows, n_all = samples.shape[0], samples.shape[1] + len(fixed)
+        n_all = n_kept + len(fixed)
         self._user_weights = weights is not None
         self.weights = weights
         if names is None:
@@ -340,7 +350,7 @@ class MCSamples(Chains):
         for ix, value in fixed:  # chains.py:1555-1559: a parameter that never moves becomes a zero-width range
             self.ranges.setFixed(self.paramNames.names[ix].name, value)
         self.paramNames.deleteIndices([ix for ix, _ in fixed])
-        self.n = samples.shape[1]
+        self.n = n_kept
         self.index = {p.name: i for i, p in enumerate(self.paramNames.names)}
         # _context_factory is a TEST hook (tests/fake_ctx.py drives the host logic on CPU); the product always uses
         # the HIP library and raises if it or a GPU is missing
@@ -434,13 +444,7 @@ class MCSamples(Chains):
                 ix = int(ignore_frac) if ignore_frac >= 1 else int(round(ch[0].shape[0] * ignore_frac))
                 ch[:] = [None if v is None else v[ix:] for v in ch]
         first = chains[0][0]
-        fixed = []
-        if first.shape[0]:
-            for i in range(first.shape[1]):
-                if np.isclose(first[0, i], first[-1, i], equal_nan=True):
-                    mean = np.average(first[:, i])
-                    if np.allclose(first[:, i], mean, rtol=1e-12, atol=0, equal_nan=True):
-                        fixed.append((i, mean))
+        fixed = self._fixed_columns(first[[0, -1]], lambda i: first[:, i]) if first.shape[0] else []
         if fixed:
             gone = [i for i, _ in fixed]
             for ch in chains:
@@ -454,6 +458,153 @@ class MCSamples(Chains):
             samples, weights, loglikes = chains[0]
         weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
         return samples, weights, loglikes, fixed
+
+    @staticmethod
+    def _fixed_columns(first_last, column):
+        """chains.py:1029-1045 on the first chain: ``first_last`` its first and last row, ``column(i)`` its column i (asked
+        for the candidates only).  Returns [(column, value)]."""
+        fixed = []
+        for i in range(first_last.shape[1]):
+            if np.isclose(first_last[0, i], first_last[-1, i], equal_nan=True):
+                col = column(i)
+                mean = np.average(col)
+                if np.allclose(col, mean, rtol=1e-12, atol=0, equal_nan=True):
+                    fixed.append((i, mean))
+        return fixed
+
+    def _read_device_chains(self, samples, weights, loglikes, ignore_lines, device, factory):
+        """
+        _read_chains for samples that live in DEVICE memory (a torch tensor on the GPU, anything with
+        __cuda_array_interface__: devarray.describe): one 2-D array, a 1-D one (a single parameter) or a list of per-chain
+        2-D arrays; ``weights`` and ``loglikes`` device or host vectors independently.  The N x n matrix never exists on
+        the host: ``ignore_rows`` moves each part's base pointer, the fixed parameters are decided from the first chain's
+        first and last row and the candidate columns (the only sample values downloaded) and left out through the kept-column
+        list, and gd_upload_device builds the resident columns and weights device to device.  Device weights and loglikes
+        are copied to the host once, as float64 vectors, for their existing host consumers.
+
+        Returns None when no device array is involved; a dict (numrows, n, weights, loglikes, fixed) when the set is
+        resident; (samples, weights, loglikes) as host arrays when the device route does not serve the input: if
+        ``min_weight_ratio`` would remove rows (this library has no device row compaction: the result is the same, only
+        slower -- everything is downloaded and the host code runs), or if the library declines the memory (page-locked,
+        managed, negative strides).
+        """
+        from . import devarray
+
+        is_list = False
+        if isinstance(samples, (list, tuple)) and len(samples):
+            d0 = devarray.describe(samples[0])
+            is_list = (np.ndim(samples[0]) if d0 is None else len(d0.shape)) == 2
+            if not is_list and any(devarray.describe(v) is not None for v in samples):
+                raise TypeError("a list of 1-D device vectors (one per parameter) is not taken: stack them into one (N, n) "
+                                "device array, or pass a list of per-chain (N_k, n) arrays")
+        chain_arrays = list(samples) if is_list else [samples]
+        per_chain = (lambda v: [None] * len(chain_arrays) if v is None else (list(v) if is_list else [v]))
+        descs = [[devarray.describe(a) for a in chain_arrays]] + [[None if a is None else devarray.describe(a) for a in per_chain(v)]
+                                                                   for v in (weights, loglikes)]
+        if not any(d is not None for row in descs for d in row):
+            return None
+        if self._column_share is not None:
+            raise MCSamplesError("column_share needs host samples: a device array is resident on one device, each rank "
+                                 "uploads its own share of the columns")
+        for d in (d for row in descs for d in row if d is not None):
+            if d.device is not None and d.device != device:
+                raise ValueError("the array lives on device %d: pass device=%d" % (d.device, d.device))
+        if self.ctx is None:
+            self.ctx = factory(device)
+        ctx = self.ctx
+
+        def to_host(obj, d, dtype=None):
+            if d is None:
+                return None if obj is None else np.asarray(obj, dtype=dtype)
+            out = ctx.fetch_device_array(d)  # (ValueError for another device's memory, an error for an unknown pointer)
+            if out is None:  # declined: memory the host can address as well -- and only that is read from here
+                from ._lib import GD_PTR_MANAGED, GD_PTR_PINNED
+
+                if ctx.pointer_info(d.ptr)[0] not in (GD_PTR_PINNED, GD_PTR_MANAGED):
+                    raise MCSamplesError("the device array is neither device memory of this device nor host-readable memory")
+                out = np.asarray(devarray.host_view(d), dtype=np.float64)
+            return out
+
+        def host_route():
+            back = [[to_host(o, d) for o, d in zip(chain_arrays, descs[0])]] + \
+                [None if v is None else [to_host(o, d, np.float64) for o, d in zip(per_chain(v), row)]
+                 for v, row in zip((weights, loglikes), descs[1:])]
+            return tuple(v if is_list or v is None else v[0] for v in back)
+
+        if any(d is None for d in descs[0]) or len({d.dtype for d in descs[0]}) != 1:
+            return host_route()  # host and device chains mixed, or chains of different element types
+        parts = [d.as2d() for d in descs[0]]
+        if any(p.shape[1] != parts[0].shape[1] for p in parts) or not parts[0].shape[1]:
+            return host_route()  # (the host code raises what it raises for such input)
+        # host copies of the weight and loglike vectors (N values each); the device descriptors of the weights stay for the
+        # resident weight column
+        host = [[None if o is None else to_host(o, d, np.float64).reshape(-1) for o, d in zip(per_chain(v), row)]
+                for v, row in zip((weights, loglikes), descs[1:])]
+        wdesc = list(descs[1])
+        for k, p in enumerate(parts):
+            for v in (host[0][k], host[1][k]):
+                if v is not None and v.shape[0] != p.shape[0]:
+                    return host_route()
+        ignore_frac = 0 if int(self.ignore_rows) else self.ignore_rows
+        mwr = self.min_weight_ratio
+
+        def drop(k, count):
+            parts[k] = parts[k].rows_from(count)
+            host[0][k], host[1][k] = (None if v is None else v[count:] for v in (host[0][k], host[1][k]))
+            if wdesc[k] is not None:
+                wdesc[k] = wdesc[k].rows_from(count)
+
+        for k in range(len(parts)):
+            if ignore_lines:
+                drop(k, ignore_lines)
+            w = host[0][k]
+            if w is not None and mwr is not None and mwr >= 0 and w.size and np.min(w) < np.max(w) * mwr:
+                return host_route()
+            if ignore_frac:
+                drop(k, int(ignore_frac) if ignore_frac >= 1 else int(round(parts[k].shape[0] * ignore_frac)))
+        numrows = sum(p.shape[0] for p in parts)
+        if numrows == 0:
+            return host_route()
+        fixed = []
+        first = parts[0]
+        if first.shape[0]:
+            ends = [ctx.fetch_device_array(first.row(i)) for i in (0, -1)]
+            if ends[0] is None:
+                return host_route()
+            fixed = self._fixed_columns(np.vstack(ends), lambda i: ctx.fetch_device_array(first.column(i)).reshape(-1))
+        gone = {i for i, _ in fixed}
+        keep = [i for i in range(first.shape[1]) if i not in gone]
+        if not keep:
+            return host_route()
+        wparts = temp = None
+        if weights is not None:
+            # a host weight vector reaches the device through a block of its own and is then described like the others
+            wparts, temp = [], []
+            for k, w in enumerate(host[0]):
+                if wdesc[k] is None:
+                    buf = ctx.alloc(max(w.nbytes, 8))
+                    buf.from_host(np.ascontiguousarray(w))
+                    temp.append(buf)
+                    wdesc[k] = devarray.DevArray(buf.ptr, w.shape, (1,), devarray.GD_DT_F64, None, None, buf)
+                wparts.append(wdesc[k])
+            if len({d.dtype for d in wparts}) != 1:  # one element type per call: the odd ones out go through their fp64 copy
+                for k, w in enumerate(host[0]):
+                    if wparts[k].dtype != devarray.GD_DT_F64:
+                        buf = ctx.alloc(max(w.nbytes, 8))
+                        buf.from_host(np.ascontiguousarray(w))
+                        temp.append(buf)
+                        wparts[k] = devarray.DevArray(buf.ptr, w.shape, (1,), devarray.GD_DT_F64, None, None, buf)
+        try:
+            if not ctx.upload_device(parts, wparts, keep if fixed else None):
+                return host_route()
+        finally:
+            for buf in temp or ():
+                buf.free()
+        if is_list:
+            self.chain_offsets = np.cumsum(np.array([0] + [p.shape[0] for p in parts]))
+        self._device_installed = True
+        stack = (lambda vs: None if vs[0] is None else np.ascontiguousarray(np.concatenate(vs), dtype=np.float64))
+        return dict(numrows=numrows, n=len(keep), weights=stack(host[0]), loglikes=stack(host[1]), fixed=fixed)
 
     # ---- state -----------------------------------------------------------------------------------------
     def _second_lane(self):
@@ -520,6 +671,14 @@ class MCSamples(Chains):
         self._loglikes_col = None  # (an extra-column slot of the old sample set)
         self.indep_thin = 0  # (a correlation length of the old sample set)
         w = self.weights
+        if self._device_installed:
+            # the constructor's device route (gd_upload_device) has installed this very set, its weight filter settled
+            # (_read_device_chains declines when the filter would remove a row): nothing to filter, nothing to upload
+            self._device_installed = False
+            self._idx_cols = {}
+            self.mean_loglike = None
+            self._like_mode = None
+            return
         if (filter_weights and self.chain_offsets is None and w is not None and self.min_weight_ratio is not None
                 and self.min_weight_ratio >= 0):
             mx, mn = np.max(w), np.min(w)  # chains.py:1017-1027
@@ -731,7 +890,7 @@ class MCSamples(Chains):
             self._setNDLimits()
         finally:
             self._loglikes_col = None
-        best = self.samples[st["argmin"]]
+        best = self._sample_row(st["argmin"])
         for j, par in enumerate(self.paramNames.names):
             par.bestfit_sample = best[j]
         self._likeStats = m

@@ -96,6 +96,52 @@ int gd_column_ptr(gd_ctx* ctx, int64_t j, void** d_out);
  *   GD_ERR_BADARG: dst == src, src without a sample set, contexts on different devices, src borrowing dst's set. */
 int gd_clone_samples(gd_ctx* dst, gd_ctx* src);
 
+/* ---------------------------------------------------------------- sample set from device memory
+ * gd_upload_device: install a sample set of the context's own from arrays that already live in DEVICE memory of the
+ *   context's device (a sampler's torch / CuPy output), without a host round trip.  The source is copied, never adopted; the
+ *   resident state afterwards is the one gd_upload leaves for the same values converted to fp64 on the host (columns
+ *   bit-equal: the conversions from fp32 / fp16 / bf16 are exact; spare columns zeroed; weights, byte multiplicities,
+ *   integral flag and weight total computed by the same code).
+ *   parts: `nparts` blocks of rows (one per chain), stacked in the order given.  Element (i, j) of a part is
+ *     base[i * row_stride + j * col_stride] (strides in ELEMENTS of `dtype`, >= 0), i < rows, j < cols; `cols` must be the
+ *     same in every part.  weights (NULL in every part, or in none): rows elements of `w_dtype`, w_stride apart.
+ *   keep / m: the source columns that become resident columns 0..m-1, in that order (NULL: all of them, m ignored).
+ *   producer_streams / nstreams: the streams that wrote the sources (none: the caller has synchronised already).  An entry
+ *     (void*)1 / (void*)2 is the legacy / per-thread default stream, anything else a hipStream_t.  An event is recorded on
+ *     each and the context's stream waits for those events; the host does not wait for a producer.  The call returns when
+ *     the copy is complete.
+ *   Everything is validated BEFORE the previous sample set is released or a kernel launched; a refusal leaves the previous
+ *   set resident.  GD_ERR_BADARG: nparts <= 0, a NULL base or negative row count, differing column counts, no rows at
+ *   all, an unknown dtype, a keep[] entry out of range, weights in some parts only, or a span (from shape and strides) that
+ *   leaves its allocation.  A valid description this call does not serve comes back with a status of its own:
+ *   GD_ERR_DECLINED for memory the HOST can read as well (page-locked, managed) and for negative strides -- the caller takes
+ *   the host route (gd_upload); GD_ERR_OTHER_DEVICE for device memory of another device than the context's (make the context
+ *   on that device); GD_ERR_NOT_DEVICE for a pointer the runtime does not know.
+ * gd_fetch_device_array: the rows x cols array described the same way, converted to fp64, into the row-major HOST array
+ *   `out` (the fixed-parameter probe's first / last row and candidate columns, device weights and loglikes).  Same
+ *   validation and statuses; producer_stream is one entry of the kind above, or NULL.
+ * gd_download_samples: the resident columns as a row-major N x n fp64 HOST array (the inverse of gd_upload; `out` should
+ *   be page-locked, gd_host_alloc): blocks of rows are transposed on the device into scratch and copied out. */
+typedef enum gd_dtype { GD_DT_F64 = 0, GD_DT_F32 = 1, GD_DT_F16 = 2, GD_DT_BF16 = 3 } gd_dtype;
+#define GD_ERR_DECLINED (-24)
+#define GD_ERR_OTHER_DEVICE (-25)
+#define GD_ERR_NOT_DEVICE (-26)
+typedef struct gd_dev_part {
+    const void* base;
+    int64_t rows, cols;
+    int64_t row_stride, col_stride;
+    const void* weights; /* may be NULL */
+    int64_t w_stride;
+} gd_dev_part;
+int gd_upload_device(gd_ctx* ctx, const gd_dev_part* parts, int32_t nparts, int32_t dtype, int32_t w_dtype,
+                     const int32_t* keep, int32_t m, void* const* producer_streams, int32_t nstreams);
+int gd_fetch_device_array(gd_ctx* ctx, const void* base, int64_t rows, int64_t cols, int64_t row_stride, int64_t col_stride,
+                          int32_t dtype, void* producer_stream, double* out);
+int gd_download_samples(gd_ctx* ctx, double* out);
+/* what the runtime says about a pointer: kind GD_PTR_*, and for device memory the device it lives on (else -1) */
+enum { GD_PTR_DEVICE = 0, GD_PTR_PINNED = 1, GD_PTR_MANAGED = 2, GD_PTR_UNKNOWN = 3 };
+int gd_pointer_info(gd_ctx* ctx, const void* ptr, int32_t* kind_out, int32_t* device_out);
+
 /* ---------------------------------------------------------------- weighted moments -------------
  * gd_weight_stats: norm=sum w (chains.py:312), max w (chains.py:1349), sum w^2 (chains.py:499,536),
  *   count of w > thresh (mcsamples.py:559-560).   out4 = {norm, max_w, sum_w2, n_above}
