@@ -166,6 +166,8 @@ SIGNATURES = {
     "gd_pointer_info": (C.c_int, [_p, _p, _pi32, _pi32]),
     "gd_fetch_device_array": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p, _pd]),
     "gd_download_samples": (C.c_int, [_p, _pd]),
+    "gd_select_samples": (C.c_int, [_p, _p, _pi64]),
+    "gd_set_weights": (C.c_int, [_p, _pd]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
@@ -239,6 +241,21 @@ class GdDevPart(C.Structure):
     _fields_ = [("base", _p), ("rows", _i64), ("cols", _i64), ("row_stride", _i64), ("col_stride", _i64), ("weights", _p),
                 ("w_stride", _i64)]
 
+
+class GdSelection(C.Structure):
+    """gd_selection of gdhip.h"""
+
+    _fields_ = [("row_kind", _i32), ("flags", _i32), ("lo", _i64), ("hi", _i64), ("rows", _p), ("K", _i64), ("thr", _f64),
+                ("keep", _p), ("m", _i32), ("append_kind", _i32), ("append_slot", _i32), ("weight_kind", _i32),
+                ("append_host", _p), ("new_weights", _p)]
+
+
+# gd_select_samples: row kinds, weight kinds, append kinds, flags, rows per tile of the count / placement passes
+GD_SEL_ALL, GD_SEL_RANGE, GD_SEL_MASK_U8, GD_SEL_WEIGHT_GT, GD_SEL_ROWS_I32 = range(5)
+GD_SEL_W_KEEP, GD_SEL_W_UNIT, GD_SEL_W_REPLACE = range(3)
+GD_SEL_APPEND_NONE, GD_SEL_APPEND_HOST, GD_SEL_APPEND_SLOT = range(3)
+GD_SEL_ROWS_ON_DEVICE = 1
+GD_SEL_TILE = 1024
 
 _lib = None
 
@@ -615,6 +632,12 @@ class Context:
         finally:
             dst.free()
 
+    def read_column(self, j):
+        """Resident column ``j`` as a host vector of N doubles"""
+        out = np.empty(self.N)
+        self._check(self.lib.gd_memcpy_d2h(self.h, out.ctypes.data, self.column_ptr(j), out.nbytes))
+        return out
+
     def upload_shard(self, cols_f, N, n, col_first, weights=None):
         """This rank's block of columns only (``cols_f``: (N, count) Fortran-ordered fp64, the columns
         [col_first, col_first + count) of the (N, n) set); the rest arrives by comm_share_columns."""
@@ -655,6 +678,82 @@ class Context:
         device to device; ``src`` may be re-uploaded or closed afterwards."""
         self._check(self.lib.gd_clone_samples(self.h, src.h))
         self.N, self.n, self.weighted = src.N, src.n, src.weighted
+
+    def select_samples(self, rows=None, keep_cols=None, append=None, weights="keep"):
+        """Replace the resident sample set by a selection of itself, device to device (gd_select_samples); returns the new
+        row count.  ``rows``: None (all), ``("range", lo, hi)``, ``("mask", m)`` with m a bool / uint8 host array of N
+        entries or a device buffer (anything with ``.ptr``) of N bytes, ``("weight_gt", thr)``, ``("rows", r)`` with r a host
+        index array or ``("rows", buf, K)`` with a device int32 buffer.  ``keep_cols``: ascending resident columns (None:
+        all).  ``append``: None, a host vector of N doubles, or ``("slot", s)`` for spare column s.  ``weights``: "keep",
+        "unit", or a host vector with one weight per selected row.  A refusal raises and leaves the set as it was."""
+        sel = GdSelection()
+        alive = []  # host arrays the structure points into
+        kind = "all" if rows is None else rows[0]
+        if kind == "range":
+            sel.row_kind, sel.lo, sel.hi = GD_SEL_RANGE, int(rows[1]), int(rows[2])
+        elif kind in ("mask", "rows"):
+            sel.row_kind = GD_SEL_MASK_U8 if kind == "mask" else GD_SEL_ROWS_I32
+            v = rows[1]
+            if hasattr(v, "ptr"):
+                sel.flags, sel.rows = GD_SEL_ROWS_ON_DEVICE, v.ptr
+                sel.K = int(rows[2]) if kind == "rows" else 0
+            else:
+                if kind == "mask":
+                    v = np.ascontiguousarray(v)
+                    v = v.view(np.uint8) if v.dtype == bool else np.ascontiguousarray(v != 0).view(np.uint8)
+                    if v.shape != (self.N,):
+                        raise ValueError("the row mask must have one entry per sample row")
+                else:
+                    v = _i32arr(v).ravel()
+                    sel.K = v.size
+                alive.append(v)
+                sel.rows = v.ctypes.data
+        elif kind == "weight_gt":
+            sel.row_kind, sel.thr = GD_SEL_WEIGHT_GT, float(rows[1])
+        elif kind != "all":
+            raise ValueError("unknown row selection %r" % (kind,))
+        n_new = self.n
+        if keep_cols is not None:
+            k = _i32arr(keep_cols).ravel()
+            alive.append(k)
+            sel.keep, sel.m, n_new = k.ctypes.data, k.size, k.size
+        if isinstance(append, tuple):
+            sel.append_kind, sel.append_slot = GD_SEL_APPEND_SLOT, int(append[1])
+            n_new += 1
+        elif append is not None:
+            a = _f64arr(append).ravel()
+            if a.shape != (self.N,):
+                raise ValueError("the appended vector must have one entry per sample row")
+            alive.append(a)
+            sel.append_kind, sel.append_host = GD_SEL_APPEND_HOST, a.ctypes.data
+            n_new += 1
+        weighted = self.weighted
+        if isinstance(weights, str):
+            if weights not in ("keep", "unit"):
+                raise ValueError("weights must be 'keep', 'unit' or a vector")
+            sel.weight_kind = GD_SEL_W_KEEP if weights == "keep" else GD_SEL_W_UNIT
+            weighted = weighted and weights == "keep"
+        else:
+            w = _f64arr(weights).ravel()
+            if sel.row_kind == GD_SEL_ROWS_I32 and w.size != sel.K:
+                raise ValueError("one new weight per selected row")
+            alive.append(w)
+            sel.weight_kind, sel.new_weights, sel.K, weighted = GD_SEL_W_REPLACE, w.ctypes.data, w.size, True
+        count = C.c_int64()
+        self._check(self.lib.gd_select_samples(self.h, C.byref(sel), C.byref(count)))
+        self._keep = None
+        self.N, self.n, self.weighted = int(count.value), int(n_new), weighted
+        return self.N
+
+    def set_weights(self, w):
+        """Replace only the sample weights of the resident set (gd_set_weights): N host doubles, or None for unit weights."""
+        if w is not None:
+            w = _f64arr(w)
+            if w.shape != (self.N,):
+                raise ValueError("weights must have one entry per sample row")
+        self._check(self.lib.gd_set_weights(self.h, None if w is None else _dp(w)))
+        self._keep = None
+        self.weighted = w is not None
 
     def bind_thread(self):
         self._check(self.lib.gd_bind_thread(self.h))

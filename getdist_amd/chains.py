@@ -141,6 +141,7 @@ class WeightedSamples:
     def samples(self, value):
         self.__dict__["_samples"] = value
         self.__dict__["_samples_on_device"] = False
+        self.__dict__["_mirror_assigned"] = True  # until the next upload the resident set is not known to equal it
 
     @property
     def _host_mirror_ready(self):
@@ -198,16 +199,90 @@ class WeightedSamples:
         self.index = {p.name: i for i, p in enumerate(self.paramNames.names)}
         self._weightsChanged(filter_weights=False)
 
+    # ---- the same edits made on the device (gd_select_samples, gd_set_weights) -----------------------------------------
+    # The resident set is replaced by a selection of itself, device to device: no fancy-indexed copy of the matrix on the
+    # host, no re-upload, and a set built from device arrays keeps doing without its host mirror.  The host vectors
+    # (weights, loglikes, chain offsets: N values each) are still made with numpy by the caller.
+    def _device_edit_applies(self):
+        """The resident set can be edited in place of the host array: a real context (the CPU tests' doubles without
+        ``select_samples`` keep the host route), every column on this device, and a host mirror that is absent or float64 (and
+        was uploaded as it is) -- then ``samples``, made again on first read (gd_download_samples), is bit for bit what numpy
+        indexing gives."""
+        if not hasattr(self.ctx, "select_samples") or getattr(self, "_column_share", None) is not None:
+            return False
+        if self.__dict__.get("_mirror_assigned"):  # ``samples`` was assigned since the last upload: the host array is the truth
+            return False
+        mirror = self.__dict__.get("_samples")
+        if mirror is None:
+            return bool(self.__dict__.get("_samples_on_device"))
+        return isinstance(mirror, np.ndarray) and mirror.dtype == np.float64 and mirror.ndim == 2
+
+    def _select_on_device(self, **selection):
+        """ctx.select_samples(**selection); afterwards the samples exist on the device only.  False when the second set does
+        not fit beside the first (the caller takes the host route); any other refusal raises with the object unchanged."""
+        from ._lib import GD_ERR_NOMEM, GdhipError
+
+        try:
+            self.ctx.select_samples(**selection)
+        except GdhipError as e:
+            if e.code != GD_ERR_NOMEM:
+                raise
+            return False
+        self.__dict__["_samples"], self.__dict__["_samples_on_device"] = None, True
+        return True
+
+    def _replace_rows(self, rows=None, keep_cols=None, append=None, weights="keep", host_weights=None, loglikes=None,
+                      chain_offsets=None):
+        """_replace_samples for a selection of the resident set itself: ``rows`` / ``keep_cols`` / ``append`` / ``weights`` as
+        Context.select_samples takes them; ``host_weights``, ``loglikes`` and ``chain_offsets`` are the host vectors of the new
+        set.  False when the device route does not apply (the caller then calls _replace_samples)."""
+        if not self._device_edit_applies():
+            return False
+        self._sample_set_changing()
+        if not self._select_on_device(rows=rows, keep_cols=keep_cols, append=append, weights=weights):
+            return False
+        self.numrows, self.n = self.ctx.N, self.ctx.n
+        if self.n != len(self.paramNames.names):
+            raise WeightedSampleError("number of sample columns does not match the parameter names")
+        self.weights = None if host_weights is None else np.ascontiguousarray(host_weights, dtype=np.float64)
+        self.loglikes = None if loglikes is None else np.ascontiguousarray(loglikes, dtype=np.float64)
+        self.chain_offsets = None if chain_offsets is None else np.asarray(chain_offsets, dtype=np.int64)
+        self.index = {p.name: i for i, p in enumerate(self.paramNames.names)}
+        self.means = self.vars = self.sddev = self.fullcov = self.correlationMatrix = None
+        self.needs_update = True
+        self.updateBaseStatistics()
+        return True
+
+    def _weights_replaced(self):
+        """_weightsChanged(filter_weights=False) for mutators that change ``self.weights`` only: the resident weight column
+        is replaced (gd_set_weights), the sample columns stay where they are."""
+        if (not hasattr(self.ctx, "set_weights") or getattr(self, "_column_share", None) is not None
+                or self.__dict__.get("_mirror_assigned")):
+            return self._weightsChanged(filter_weights=False)
+        self.means = self.vars = self.sddev = self.fullcov = self.correlationMatrix = None
+        self._sample_set_changing()
+        self.ctx.set_weights(self.weights)
+        self.needs_update = True
+        self.updateBaseStatistics()
+
     def _host_weights(self):
         return self.weights if self.weights is not None else np.ones(self.numrows)
 
     def thin(self, factor):
         """chains.py:941-952: thin by ``factor`` to unit-weight samples (integer weights).  The thinned row list comes
         from the device (gd_thin_rows); chain boundaries follow the rows that survive."""
-        thin_ix = self.thin_indices(factor)
-        offsets = None if self.chain_offsets is None else np.searchsorted(thin_ix, self.chain_offsets)
-        self._replace_samples(self.samples[thin_ix, :], None,
-                              None if self.loglikes is None else self.loglikes[thin_ix], offsets)
+        if not self.ctx.weights_integral():
+            raise WeightedSampleError("Can only thin with integer weights")
+        buf, K = self._thin_rows(factor)  # (the list goes into the selection as it lies in device memory)
+        try:
+            thin_ix = buf.to_host((K,), dtype=np.int32).astype(np.int64) if K else np.zeros(0, dtype=np.int64)
+            offsets = None if self.chain_offsets is None else np.searchsorted(thin_ix, self.chain_offsets)
+            loglikes = None if self.loglikes is None else self.loglikes[thin_ix]
+            if K and self._replace_rows(rows=("rows", buf, K), weights="unit", loglikes=loglikes, chain_offsets=offsets):
+                return
+        finally:
+            buf.free()
+        self._replace_samples(self.samples[thin_ix, :], None, loglikes, offsets)
 
     def weighted_thin(self, factor):
         """chains.py:954-966,1188-1206: thin by ``factor`` keeping integer multiplicities; separate chains are thinned
@@ -224,8 +299,11 @@ class WeightedSamples:
             rows.append(u), counts.append(c), lens.append(len(u))
         rows, counts = np.concatenate(rows), np.concatenate(counts)
         offsets = None if self.chain_offsets is None else np.cumsum(lens)
-        self._replace_samples(self.samples[rows, :], counts.astype(np.float64),
-                              None if self.loglikes is None else self.loglikes[rows], offsets)
+        counts, loglikes = counts.astype(np.float64), None if self.loglikes is None else self.loglikes[rows]
+        if rows.size and self._replace_rows(rows=("rows", rows), weights=counts, host_weights=counts, loglikes=loglikes,
+                                            chain_offsets=offsets):
+            return
+        self._replace_samples(self.samples[rows, :], counts, loglikes, offsets)
 
     def filter(self, where):
         """chains.py:968-979,1174-1186: keep the rows ``where`` (boolean mask, row indices, or a boolean column expression,
@@ -241,6 +319,19 @@ class WeightedSamples:
                 offsets = np.cumsum([0] + [int(np.count_nonzero(where[a:b])) for a, b in self._chain_ranges()])
             elif where.size == 0 or np.all(np.diff(where) > 0):
                 offsets = np.searchsorted(where, self.chain_offsets)
+        # the device route serves what numpy would accept without a doubt: a mask of one entry per row, or in-range integer
+        # indices (negative ones counted from the end); anything else goes to numpy, whose error it then is
+        rows = None
+        if where.dtype == bool and where.shape == (self.numrows,):
+            rows = ("mask", where)
+        elif (where.ndim == 1 and where.size and where.dtype.kind in "iu" and where.min() >= -self.numrows
+              and where.max() < self.numrows):
+            rows = ("rows", np.where(where < 0, where + self.numrows, where))
+        if rows is not None and self._device_edit_applies():
+            weights = None if self.weights is None else self.weights[where]
+            if self._replace_rows(rows=rows, host_weights=weights, loglikes=None if self.loglikes is None else self.loglikes[where],
+                                  chain_offsets=offsets):
+                return
         self._replace_samples(self.samples[where, :], None if self.weights is None else self.weights[where],
                               None if self.loglikes is None else self.loglikes[where], offsets)
 
@@ -267,7 +358,7 @@ class WeightedSamples:
         if self.loglikes is not None:
             self.loglikes = self.loglikes + logLikes
         self.weights = self._host_weights() * np.exp(-(logLikes - scale))
-        self._weightsChanged(filter_weights=False)
+        self._weights_replaced()
 
     def cool(self, cool=None):
         """mcsamples.py:533-550 + chains.py:995-1008: multiply the log-likelihoods by ``cool`` and re-weight"""
@@ -285,7 +376,7 @@ class WeightedSamples:
         newL = self.loglikes * cool
         self.weights = self._host_weights() * np.exp(-(newL - self.loglikes) - (MaxL * (1 - cool)))
         self.loglikes = newL
-        self._weightsChanged(filter_weights=False)
+        self._weights_replaced()
         self.cooled = cool
         if self.temperature is not None:
             self.temperature = float(self.temperature) / cool
@@ -300,24 +391,46 @@ class WeightedSamples:
             offsets = np.unique(np.maximum(self.chain_offsets - ix, 0))
             if len(offsets) < 2:
                 offsets = None
-        self._replace_samples(self.samples[ix:, :], None if self.weights is None else self.weights[ix:],
-                              None if self.loglikes is None else self.loglikes[ix:], offsets)
+        weights, loglikes = (None if v is None else v[ix:] for v in (self.weights, self.loglikes))
+        if 0 <= ix < self.numrows and self._replace_rows(rows=("range", ix, self.numrows), host_weights=weights, loglikes=loglikes,
+                                                          chain_offsets=offsets):
+            return
+        self._replace_samples(self.samples[ix:, :], weights, loglikes, offsets)
+
+    def removeBurnFraction(self, ignore_frac):
+        """chains.py:1529-1543: remove the burn-in fraction (or number of rows) from every chain.  The chains of this library
+        are always combined into one stacked set, for which the reference removes the rows from the front of it."""
+        self.removeBurn(ignore_frac)
+        self.needs_update = True
 
     def deleteFixedParams(self):
         """chains.py:1029-1045,1544-1559: remove the parameters that do not vary (they become zero-width ranges).
         Returns (indices removed, their values)."""
         fixed, values = [], []
-        for i in range(self.samples.shape[1]):
-            if np.isclose(self.samples[0, i], self.samples[-1, i], equal_nan=True):
-                mean = np.average(self.samples[:, i])
-                if np.allclose(self.samples[:, i], mean, rtol=1e-12, atol=0, equal_nan=True):
+        on_device = self._device_edit_applies()
+        if on_device and not self._host_mirror_ready:
+            # fixedness without the host mirror, by the probe of the constructor's device route: the first and the last row,
+            # then the candidate columns only
+            first, last = self.ctx.read_row(0), self.ctx.read_row(self.numrows - 1)
+            column = self.ctx.read_column
+        else:
+            first, last = self.samples[0], self.samples[-1]
+            column = (lambda i: self.samples[:, i])
+        for i in range(self.n):
+            if np.isclose(first[i], last[i], equal_nan=True):
+                col = column(i)
+                mean = np.average(col)
+                if np.allclose(col, mean, rtol=1e-12, atol=0, equal_nan=True):
                     fixed.append(i)
                     values.append(mean)
         if fixed:
+            keep = [i for i in range(self.n) if i not in fixed]
             for ix, value in zip(fixed, values):
                 self.ranges.setFixed(self.paramNames.names[ix].name, value)
             self.paramNames.deleteIndices(fixed)
-            self._replace_samples(np.delete(self.samples, fixed, 1), self.weights, self.loglikes, self.chain_offsets)
+            if not (on_device and keep and self._replace_rows(keep_cols=keep, host_weights=self.weights, loglikes=self.loglikes,
+                                                              chain_offsets=self.chain_offsets)):
+                self._replace_samples(np.delete(self.samples, fixed, 1), self.weights, self.loglikes, self.chain_offsets)
         return fixed, values
 
     # ---- name and label (chains.py:260-273) ------------------------------------------------------------------
@@ -964,6 +1077,18 @@ class Chains(WeightedSamples):
         expression evaluated on the device and fetched).  Returns its ParamInfo."""
         if self.paramNames.parWithName(name):
             raise ValueError("Parameter with name %s already exists" % name)
+        par = ParamInfo(name, label or None)
+        par.isDerived, par.comment = True, comment
+        if _is_expr(paramVec) and self._device_edit_applies():
+            # the expression is evaluated into a spare column and appended from there: its values never cross PCIe
+            paramVec.to_column(self, 0)
+            if range is not None:
+                self.ranges.setRange(name, range)
+            self.paramNames.names.append(par)
+            if self._replace_rows(append=("slot", 0), host_weights=self.weights, loglikes=self.loglikes,
+                                  chain_offsets=self.chain_offsets):
+                return par
+            self.paramNames.names.pop()
         if _is_expr(paramVec):
             paramVec = paramVec.eval(self)
         vec = np.asarray(paramVec, dtype=np.float64).reshape(-1)
@@ -971,12 +1096,12 @@ class Chains(WeightedSamples):
             raise WeightedSampleError("derived parameter vector must have one entry per sample")
         if range is not None:
             self.ranges.setRange(name, range)
+        self.paramNames.names.append(par)
+        if self._replace_rows(append=vec, host_weights=self.weights, loglikes=self.loglikes, chain_offsets=self.chain_offsets):
+            return par
         new = np.empty((self.numrows, self.n + 1), dtype=np.float64, order="F")  # the device layout: no transpose
         new[:, :self.n] = self.samples
         new[:, self.n] = vec
-        par = ParamInfo(name, label or None)
-        par.isDerived, par.comment = True, comment
-        self.paramNames.names.append(par)
         self._replace_samples(new, self.weights, self.loglikes, self.chain_offsets)
         return par
 

@@ -484,9 +484,9 @@ class MCSamples(Chains):
 
         Returns None when no device array is involved; a dict (numrows, n, weights, loglikes, fixed) when the set is
         resident; (samples, weights, loglikes) as host arrays when the device route does not serve the input: if
-        ``min_weight_ratio`` would remove rows (this library has no device row compaction: the result is the same, only
-        slower -- everything is downloaded and the host code runs), or if the library declines the memory (page-locked,
-        managed, negative strides).
+        ``min_weight_ratio`` would remove rows (the constructor keeps the host route for that, as the per-chain filter runs
+        before the chains are stacked: the result is the same, only slower -- everything is downloaded and the host code
+        runs), or if the library declines the memory (page-locked, managed, negative strides).
         """
         from . import devarray
 
@@ -663,27 +663,45 @@ class MCSamples(Chains):
             self._twin = None
         self._nlanes = 1
 
-    def _upload(self, filter_weights=True):
-        """(Re)build the device mirror of samples/weights (chains.py:276-323 funnel).  The min-weight filter of
-        setSamples applies to a single sample array only: chain lists are filtered per chain before they are stacked."""
+    def _sample_set_changing(self):
+        """The bookkeeping every replacement of the resident samples or weights shares (a re-upload, and the device-to-device
+        edits of chains.py): the second lane borrows the set, and everything cached about it is stale."""
         self._drop_second_lane()
         self._chain_stats_cache = {}
         self._loglikes_col = None  # (an extra-column slot of the old sample set)
         self.indep_thin = 0  # (a correlation length of the old sample set)
+        self._idx_cols = {}
+        self.mean_loglike = None  # chains.py:317; recomputed on the device when a mean-likelihood is asked for
+        self._like_mode = None
+
+    def _upload(self, filter_weights=True):
+        """(Re)build the device mirror of samples/weights (chains.py:276-323 funnel).  The min-weight filter of
+        setSamples applies to a single sample array only: chain lists are filtered per chain before they are stacked."""
+        self._sample_set_changing()
+        self.__dict__["_mirror_assigned"] = False  # (whatever ``samples`` holds is what is resident when this returns)
         w = self.weights
         if self._device_installed:
             # the constructor's device route (gd_upload_device) has installed this very set, its weight filter settled
             # (_read_device_chains declines when the filter would remove a row): nothing to filter, nothing to upload
             self._device_installed = False
-            self._idx_cols = {}
-            self.mean_loglike = None
-            self._like_mode = None
             return
         if (filter_weights and self.chain_offsets is None and w is not None and self.min_weight_ratio is not None
                 and self.min_weight_ratio >= 0):
             mx, mn = np.max(w), np.min(w)  # chains.py:1017-1027
             if mn < mx * self.min_weight_ratio:
-                keep = w > mx * self.min_weight_ratio
+                thr = mx * self.min_weight_ratio
+                if self._device_edit_applies() and np.any(w > thr):
+                    # the whole array goes up as it is and the rows are dropped there (GD_SEL_WEIGHT_GT, the same comparison
+                    # on the resident weights): no fancy-indexed copy of the matrix on the host
+                    self.ctx.upload(self.samples, w)
+                    if self._select_on_device(rows=("weight_gt", thr)):
+                        keep = w > thr
+                        self.weights = w[keep]
+                        if self.loglikes is not None:
+                            self.loglikes = self.loglikes[keep]
+                        self.numrows = self.ctx.N
+                        return
+                keep = w > thr
                 self.samples = self.samples[keep]
                 self.weights = w = w[keep]
                 if self.loglikes is not None:
@@ -694,9 +712,6 @@ class MCSamples(Chains):
             share.upload(self.ctx, self.samples, w)  # (collective: every rank of the job uploads at the same point)
         else:
             self.ctx.upload(self.samples, w)
-        self._idx_cols = {}
-        self.mean_loglike = None  # chains.py:317; recomputed on the device when a mean-likelihood is asked for
-        self._like_mode = None
 
     def parName(self, i, starDerived=False):
         """mcsamples.py:348-356: the name of parameter ``i``, with a trailing * for a derived one when ``starDerived``"""

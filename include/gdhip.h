@@ -142,6 +142,64 @@ int gd_download_samples(gd_ctx* ctx, double* out);
 enum { GD_PTR_DEVICE = 0, GD_PTR_PINNED = 1, GD_PTR_MANAGED = 2, GD_PTR_UNKNOWN = 3 };
 int gd_pointer_info(gd_ctx* ctx, const void* ptr, int32_t* kind_out, int32_t* device_out);
 
+/* ---------------------------------------------------------------- editing the resident sample set
+ * gd_select_samples: replace the context's OWN resident sample set by a selection of itself, device to device: the rows a
+ *   mutator keeps (filter, thin, removeBurn: chains.py:941-1061), the columns it keeps (deleteFixedParams) and at most one
+ *   appended column (addDerived).  The resident state afterwards is the one gd_upload leaves for the same selection made
+ *   with numpy on the host (columns and weights bit-equal, spare columns zeroed, integral flag, weight total and byte
+ *   multiplicities computed by the same code, no cached prefix sums, bucket or index columns, no auxiliary weights).
+ *   Rows (row_kind):
+ *     GD_SEL_ALL        every row.
+ *     GD_SEL_RANGE      rows [lo, hi).
+ *     GD_SEL_MASK_U8    `rows` is N bytes; the rows whose byte != 0, in ascending order.
+ *     GD_SEL_WEIGHT_GT  the rows whose sample weight > thr (evaluated on the resident weight column; a unit-weight set
+ *                       has weight 1 in every row), in ascending order.
+ *     GD_SEL_ROWS_I32   `rows` is a list of K int32 row numbers: any order, repeats allowed, K may exceed N (what
+ *                       gd_thin_rows writes).
+ *     flags & GD_SEL_ROWS_ON_DEVICE: `rows` (mask or list) is device memory of the context's device, else host memory.  A
+ *     host list is checked against [0, N); a device list is trusted, as gd_gather_rows trusts it.
+ *   Columns: keep[m] are the resident columns that stay, ascending (NULL: all n, m ignored).  append_kind
+ *     GD_SEL_APPEND_HOST puts the host vector append_host (N doubles, one per row of the CURRENT set) behind them,
+ *     GD_SEL_APPEND_SLOT the spare column append_slot (where gd_expr_eval(..., GD_EX_TO_COLUMN, slot) leaves an
+ *     expression); the appended column goes through the same row selection.
+ *   Weights (weight_kind): GD_SEL_W_KEEP selects the weight column like a sample column (none stays none);
+ *     GD_SEL_W_UNIT leaves the new set without weights; GD_SEL_W_REPLACE takes new_weights, one double per SELECTED row
+ *     (K must then state their number for every row kind, and is checked against the count selected).
+ *   Ordered selections (mask, weight threshold) become a device int32 row list first -- a count per tile of 1024 rows, an
+ *   exclusive scan of the tile counts, an ordered placement by wave ballot -- and one gather kernel moves the data;
+ *   GD_SEL_ALL / GD_SEL_RANGE are device-to-device copies per column.  The new set is built beside the old one and installed
+ *   when complete; the call returns when it is.  *count_out (may be NULL) receives the new row count.
+ *   Refusals leave the previous set resident and untouched.  GD_ERR_BADARG: no resident set, a borrowed one
+ *   (gd_attach_samples), auxiliary weights selected, N >= 2^31, lo / hi outside [0, N] or lo >= hi, a keep[] entry out of
+ *   range or not ascending, no column left (m + appended == 0), an unknown kind, a missing pointer, GD_SEL_W_REPLACE
+ *   without a vector or with a K that is not the count selected, a host row number outside [0, N), and no row selected
+ *   ("no rows selected").  GD_ERR_NOMEM when the second set does not fit beside the first.
+ * gd_set_weights: replace only the SAMPLE WEIGHT column of the context's own resident set by the N host doubles w_host
+ *   (NULL: unit weights, no weight column).  Integral flag, total and byte multiplicities are recomputed as by an upload;
+ *   everything cached that depends on the weights goes (cumulative weights, auxiliary / like weights, the batched call's
+ *   index columns, the bucket columns -- their bucket count follows the weight mode); the sample columns are not touched.
+ *   GD_ERR_BADARG for no resident set, a borrowed one, or while auxiliary weights are selected. */
+enum { GD_SEL_ALL = 0, GD_SEL_RANGE = 1, GD_SEL_MASK_U8 = 2, GD_SEL_WEIGHT_GT = 3, GD_SEL_ROWS_I32 = 4 };
+enum { GD_SEL_W_KEEP = 0, GD_SEL_W_UNIT = 1, GD_SEL_W_REPLACE = 2 };
+enum { GD_SEL_APPEND_NONE = 0, GD_SEL_APPEND_HOST = 1, GD_SEL_APPEND_SLOT = 2 };
+#define GD_SEL_ROWS_ON_DEVICE 1
+#define GD_SEL_TILE 1024 /* rows per tile of the count / placement passes */
+typedef struct gd_selection {
+    int32_t row_kind, flags;
+    int64_t lo, hi;      /* GD_SEL_RANGE */
+    const void* rows;    /* GD_SEL_MASK_U8: N bytes; GD_SEL_ROWS_I32: K int32 */
+    int64_t K;           /* GD_SEL_ROWS_I32: the list's length; with GD_SEL_W_REPLACE: the number of new weights */
+    double thr;          /* GD_SEL_WEIGHT_GT */
+    const int32_t* keep; /* may be NULL */
+    int32_t m;
+    int32_t append_kind, append_slot;
+    int32_t weight_kind;
+    const double* append_host;
+    const double* new_weights;
+} gd_selection;
+int gd_select_samples(gd_ctx* ctx, const gd_selection* sel, int64_t* count_out);
+int gd_set_weights(gd_ctx* ctx, const double* w_host);
+
 /* ---------------------------------------------------------------- weighted moments -------------
  * gd_weight_stats: norm=sum w (chains.py:312), max w (chains.py:1349), sum w^2 (chains.py:499,536),
  *   count of w > thresh (mcsamples.py:559-560).   out4 = {norm, max_w, sum_w2, n_above}
