@@ -173,36 +173,21 @@ class WeightedSamples:
         """chains.py:302-308"""
         self.setSamples(samples, self.weights, self.loglikes)
 
-    def _weightsChanged(self, filter_weights=True):
-        """chains.py:310-323: everything derived from samples/weights is stale; re-upload and recompute.  The
-        min-weight filter belongs to setSamples (chains.py:296-299), not to the reference's _weightsChanged: mutators
-        that call that directly (reweightAddingLogLikes, cool) pass filter_weights=False."""
+    def _weightsChanged(self, filter_weights=True, resident=False):
+        """chains.py:310-323: everything derived from samples/weights is stale; re-upload (unless an edit on the device has
+        left the ``resident`` set what the host state says) and recompute.  The min-weight filter belongs to setSamples
+        (chains.py:296-299), not to the reference's _weightsChanged: mutators that call that directly
+        (reweightAddingLogLikes, cool) pass filter_weights=False."""
         self.means = self.vars = self.sddev = self.fullcov = self.correlationMatrix = None
-        self._upload(filter_weights=filter_weights)
+        if not resident:
+            self._upload(filter_weights=filter_weights)
         self.needs_update = True
         self.updateBaseStatistics()
 
-    # ---- mutators of the sample set (SURVEY.md 8b, state invalidation): every one funnels into a re-upload -------
-    def _replace_samples(self, samples, weights, loglikes, chain_offsets=None):
-        """setSamples(..., min_weight_ratio=-1) of the reference's mutators (no weight filter), for a sample array whose
-        row AND column counts may have changed; the device mirror and every derived cache are rebuilt."""
-        samples = np.asarray(samples)
-        if samples.ndim == 1:
-            samples = samples.reshape(-1, 1)
-        if samples.shape[1] != len(self.paramNames.names):
-            raise WeightedSampleError("number of sample columns does not match the parameter names")
-        self.samples = samples
-        self.numrows, self.n = samples.shape
-        self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
-        self.loglikes = None if loglikes is None else np.ascontiguousarray(loglikes, dtype=np.float64)
-        self.chain_offsets = None if chain_offsets is None else np.asarray(chain_offsets, dtype=np.int64)
-        self.index = {p.name: i for i, p in enumerate(self.paramNames.names)}
-        self._weightsChanged(filter_weights=False)
-
-    # ---- the same edits made on the device (gd_select_samples, gd_set_weights) -----------------------------------------
-    # The resident set is replaced by a selection of itself, device to device: no fancy-indexed copy of the matrix on the
-    # host, no re-upload, and a set built from device arrays keeps doing without its host mirror.  The host vectors
-    # (weights, loglikes, chain offsets: N values each) are still made with numpy by the caller.
+    # ---- mutators of the sample set (SURVEY.md 8b, state invalidation): every one states its edit once, to _edit_samples ----
+    # Where it can, the resident set is replaced by a selection of itself, device to device (gd_select_samples): no
+    # fancy-indexed copy of the matrix on the host, no re-upload, and a set built from device arrays keeps doing without its
+    # host mirror.  Otherwise the same edit is made on the host array with numpy and uploaded.
     def _device_edit_applies(self):
         """The resident set can be edited in place of the host array: a real context (the CPU tests' doubles without
         ``select_samples`` keep the host route), every column on this device, and a host mirror that is absent or float64 (and
@@ -231,39 +216,57 @@ class WeightedSamples:
         self.__dict__["_samples"], self.__dict__["_samples_on_device"] = None, True
         return True
 
-    def _replace_rows(self, rows=None, keep_cols=None, append=None, weights="keep", host_weights=None, loglikes=None,
-                      chain_offsets=None):
-        """_replace_samples for a selection of the resident set itself: ``rows`` / ``keep_cols`` / ``append`` / ``weights`` as
-        Context.select_samples takes them; ``host_weights``, ``loglikes`` and ``chain_offsets`` are the host vectors of the new
-        set.  False when the device route does not apply (the caller then calls _replace_samples)."""
-        if not self._device_edit_applies():
-            return False
-        self._sample_set_changing()
-        if not self._select_on_device(rows=rows, keep_cols=keep_cols, append=append, weights=weights):
-            return False
-        self.numrows, self.n = self.ctx.N, self.ctx.n
-        if self.n != len(self.paramNames.names):
+    def _edit_samples(self, rows=None, keep_cols=None, append=None, weights="keep", chain_offsets=None, index=None, device=True):
+        """The sample set becomes a selection of itself.  ``rows`` / ``keep_cols`` / ``weights`` as Context.select_samples takes
+        them; ``append`` too, a host vector or ``("slot", s, expr)`` with the expression that spare column s was evaluated
+        from (the host route fetches its values); ``chain_offsets`` are those of the result.  ``index`` is what numpy indexes
+        the rows with, where ``rows`` does not say it (a device row list) or only numpy can judge it; ``device`` is the
+        caller's own condition for the device route, which is taken when _device_edit_applies and the second set fits beside
+        the first, else the same edit is made on the host array and uploaded.  The new host weights and loglikes are the old
+        ones at ``index``, so a selection numpy refuses raises numpy's error before anything has changed."""
+        if index is None:
+            index = slice(None) if rows is None else slice(rows[1], rows[2]) if rows[0] == "range" else rows[1]
+        if isinstance(weights, str):
+            weights_new = None if weights == "unit" or self.weights is None else self.weights[index]
+        else:
+            weights_new = weights
+        loglikes = None if self.loglikes is None else self.loglikes[index]
+        on_device = device and self._device_edit_applies()
+        if on_device:
+            self._sample_set_changing()
+            on_device = self._select_on_device(rows=rows, keep_cols=keep_cols, append=append, weights=weights)
+        if on_device:
+            numrows, n = self.ctx.N, self.ctx.n
+        else:
+            samples = self.samples[index, :]
+            if keep_cols is not None:
+                samples = np.delete(samples, np.setdiff1d(np.arange(self.n), keep_cols), 1)
+            if append is not None:
+                old = samples
+                samples = np.empty((old.shape[0], old.shape[1] + 1), dtype=np.float64, order="F")  # the device layout: no transpose
+                samples[:, :-1] = old
+                samples[:, -1] = append[2].eval(self) if isinstance(append, tuple) else append
+            numrows, n = samples.shape
+        if n != len(self.paramNames.names):
             raise WeightedSampleError("number of sample columns does not match the parameter names")
-        self.weights = None if host_weights is None else np.ascontiguousarray(host_weights, dtype=np.float64)
+        if not on_device:
+            self.samples = samples
+        self.numrows, self.n = numrows, n
+        self.weights = None if weights_new is None else np.ascontiguousarray(weights_new, dtype=np.float64)
         self.loglikes = None if loglikes is None else np.ascontiguousarray(loglikes, dtype=np.float64)
         self.chain_offsets = None if chain_offsets is None else np.asarray(chain_offsets, dtype=np.int64)
         self.index = {p.name: i for i, p in enumerate(self.paramNames.names)}
-        self.means = self.vars = self.sddev = self.fullcov = self.correlationMatrix = None
-        self.needs_update = True
-        self.updateBaseStatistics()
-        return True
+        self._weightsChanged(filter_weights=False, resident=on_device)
 
     def _weights_replaced(self):
         """_weightsChanged(filter_weights=False) for mutators that change ``self.weights`` only: the resident weight column
         is replaced (gd_set_weights), the sample columns stay where they are."""
-        if (not hasattr(self.ctx, "set_weights") or getattr(self, "_column_share", None) is not None
-                or self.__dict__.get("_mirror_assigned")):
-            return self._weightsChanged(filter_weights=False)
-        self.means = self.vars = self.sddev = self.fullcov = self.correlationMatrix = None
-        self._sample_set_changing()
-        self.ctx.set_weights(self.weights)
-        self.needs_update = True
-        self.updateBaseStatistics()
+        resident = (hasattr(self.ctx, "set_weights") and getattr(self, "_column_share", None) is None
+                    and not self.__dict__.get("_mirror_assigned"))
+        if resident:
+            self._sample_set_changing()
+            self.ctx.set_weights(self.weights)
+        self._weightsChanged(filter_weights=False, resident=resident)
 
     def _host_weights(self):
         return self.weights if self.weights is not None else np.ones(self.numrows)
@@ -277,12 +280,9 @@ class WeightedSamples:
         try:
             thin_ix = buf.to_host((K,), dtype=np.int32).astype(np.int64) if K else np.zeros(0, dtype=np.int64)
             offsets = None if self.chain_offsets is None else np.searchsorted(thin_ix, self.chain_offsets)
-            loglikes = None if self.loglikes is None else self.loglikes[thin_ix]
-            if K and self._replace_rows(rows=("rows", buf, K), weights="unit", loglikes=loglikes, chain_offsets=offsets):
-                return
+            self._edit_samples(rows=("rows", buf, K), index=thin_ix, weights="unit", chain_offsets=offsets, device=K > 0)
         finally:
             buf.free()
-        self._replace_samples(self.samples[thin_ix, :], None, loglikes, offsets)
 
     def weighted_thin(self, factor):
         """chains.py:954-966,1188-1206: thin by ``factor`` keeping integer multiplicities; separate chains are thinned
@@ -299,11 +299,7 @@ class WeightedSamples:
             rows.append(u), counts.append(c), lens.append(len(u))
         rows, counts = np.concatenate(rows), np.concatenate(counts)
         offsets = None if self.chain_offsets is None else np.cumsum(lens)
-        counts, loglikes = counts.astype(np.float64), None if self.loglikes is None else self.loglikes[rows]
-        if rows.size and self._replace_rows(rows=("rows", rows), weights=counts, host_weights=counts, loglikes=loglikes,
-                                            chain_offsets=offsets):
-            return
-        self._replace_samples(self.samples[rows, :], counts, loglikes, offsets)
+        self._edit_samples(rows=("rows", rows), weights=counts.astype(np.float64), chain_offsets=offsets, device=rows.size > 0)
 
     def filter(self, where):
         """chains.py:968-979,1174-1186: keep the rows ``where`` (boolean mask, row indices, or a boolean column expression,
@@ -327,13 +323,7 @@ class WeightedSamples:
         elif (where.ndim == 1 and where.size and where.dtype.kind in "iu" and where.min() >= -self.numrows
               and where.max() < self.numrows):
             rows = ("rows", np.where(where < 0, where + self.numrows, where))
-        if rows is not None and self._device_edit_applies():
-            weights = None if self.weights is None else self.weights[where]
-            if self._replace_rows(rows=rows, host_weights=weights, loglikes=None if self.loglikes is None else self.loglikes[where],
-                                  chain_offsets=offsets):
-                return
-        self._replace_samples(self.samples[where, :], None if self.weights is None else self.weights[where],
-                              None if self.loglikes is None else self.loglikes[where], offsets)
+        self._edit_samples(rows=rows, index=where, chain_offsets=offsets, device=rows is not None)
 
     def deleteZeros(self):
         """chains.py:1010-1015"""
@@ -391,11 +381,7 @@ class WeightedSamples:
             offsets = np.unique(np.maximum(self.chain_offsets - ix, 0))
             if len(offsets) < 2:
                 offsets = None
-        weights, loglikes = (None if v is None else v[ix:] for v in (self.weights, self.loglikes))
-        if 0 <= ix < self.numrows and self._replace_rows(rows=("range", ix, self.numrows), host_weights=weights, loglikes=loglikes,
-                                                          chain_offsets=offsets):
-            return
-        self._replace_samples(self.samples[ix:, :], weights, loglikes, offsets)
+        self._edit_samples(rows=("range", ix, self.numrows), chain_offsets=offsets, device=0 <= ix < self.numrows)
 
     def removeBurnFraction(self, ignore_frac):
         """chains.py:1529-1543: remove the burn-in fraction (or number of rows) from every chain.  The chains of this library
@@ -428,9 +414,7 @@ class WeightedSamples:
             for ix, value in zip(fixed, values):
                 self.ranges.setFixed(self.paramNames.names[ix].name, value)
             self.paramNames.deleteIndices(fixed)
-            if not (on_device and keep and self._replace_rows(keep_cols=keep, host_weights=self.weights, loglikes=self.loglikes,
-                                                              chain_offsets=self.chain_offsets)):
-                self._replace_samples(np.delete(self.samples, fixed, 1), self.weights, self.loglikes, self.chain_offsets)
+            self._edit_samples(keep_cols=keep, chain_offsets=self.chain_offsets, device=bool(keep))
         return fixed, values
 
     # ---- name and label (chains.py:260-273) ------------------------------------------------------------------
@@ -1082,27 +1066,17 @@ class Chains(WeightedSamples):
         if _is_expr(paramVec) and self._device_edit_applies():
             # the expression is evaluated into a spare column and appended from there: its values never cross PCIe
             paramVec.to_column(self, 0)
-            if range is not None:
-                self.ranges.setRange(name, range)
-            self.paramNames.names.append(par)
-            if self._replace_rows(append=("slot", 0), host_weights=self.weights, loglikes=self.loglikes,
-                                  chain_offsets=self.chain_offsets):
-                return par
-            self.paramNames.names.pop()
-        if _is_expr(paramVec):
-            paramVec = paramVec.eval(self)
-        vec = np.asarray(paramVec, dtype=np.float64).reshape(-1)
-        if vec.shape != (self.numrows,):
-            raise WeightedSampleError("derived parameter vector must have one entry per sample")
+            append = ("slot", 0, paramVec)
+        else:
+            if _is_expr(paramVec):
+                paramVec = paramVec.eval(self)
+            append = np.asarray(paramVec, dtype=np.float64).reshape(-1)
+            if append.shape != (self.numrows,):
+                raise WeightedSampleError("derived parameter vector must have one entry per sample")
         if range is not None:
             self.ranges.setRange(name, range)
         self.paramNames.names.append(par)
-        if self._replace_rows(append=vec, host_weights=self.weights, loglikes=self.loglikes, chain_offsets=self.chain_offsets):
-            return par
-        new = np.empty((self.numrows, self.n + 1), dtype=np.float64, order="F")  # the device layout: no transpose
-        new[:, :self.n] = self.samples
-        new[:, self.n] = vec
-        self._replace_samples(new, self.weights, self.loglikes, self.chain_offsets)
+        self._edit_samples(append=append, chain_offsets=self.chain_offsets)
         return par
 
     # ---- text export (chains.py:1562-1581) -------------------------------------------------------------------

@@ -214,7 +214,7 @@ __global__ void __launch_bounds__(CP_THREADS) k_cp_count(const CpTask* __restric
             }
         }
     }
-    if (lane == 0) red[wv] = c;
+    const int n = block_sum(lane == 0 ? c : 0, red);  // c is the wave's count in every lane
     int bad = 0;
     if (tk.first) {
         const int cells = g.ny * g.nx;
@@ -222,8 +222,6 @@ __global__ void __launch_bounds__(CP_THREADS) k_cp_count(const CpTask* __restric
     }
     bad = __syncthreads_or(bad);
     if (threadIdx.x == 0) {
-        int n = 0;
-        for (int k = 0; k < CP_WAVES; ++k) n += red[k];
         cnt[t] = n;
         big[t] = n > CP_LDS_SLOTS ? (n + 1) & ~1 : 0;
         if (tk.first) status[tk.grid] = bad ? 1 : 0;
@@ -450,13 +448,9 @@ int gd_contour_paths(gd_ctx* ctx, int32_t B, const void* d_grids, const int64_t*
     long long *d_cnt = (long long*)(base + o_cnt), *d_big = (long long*)(base + o_big), *d_nl = (long long*)(base + o_nl);
     k_cp_count<<<T, CP_THREADS, 0, ctx->stream>>>(d_tasks, d_order, d_cnt, d_big, (int*)(base + o_st), d_bits, d_pre);
     GD_KERNEL_CHECK();
-    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(d_cnt, T);
-    GD_KERNEL_CHECK();
-    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(d_big, T);
-    GD_KERNEL_CHECK();
     long long V = 0, Vbig = 0, L = 0;
-    GD_TRY(gd_fetch(ctx, &V, d_cnt + T, 8));
-    GD_TRY(gd_fetch(ctx, &Vbig, d_big + T, 8));
+    GD_TRY(gd_tile_offsets(ctx, d_cnt, T, &V));
+    GD_TRY(gd_tile_offsets(ctx, d_big, T, &Vbig));
     GD_TRY(gd_fetch(ctx, status_out, base + o_st, (size_t)B * 4));
     GD_TRY(gd_stream_sync(ctx));  // the meta block was pageable: the copy has read it by now
     for (int t = 0; t <= T; ++t) task_vert_off[t] = task_loop_off[t] = 0;
@@ -473,11 +467,9 @@ int gd_contour_paths(gd_ctx* ctx, int32_t B, const void* d_grids, const int64_t*
                                                   (double2*)(work + o_xy), (unsigned char*)(work + o_flag), (int*)(work + o_ls),
                                                   d_nl);
     GD_KERNEL_CHECK();
-    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(d_nl, T);
-    GD_KERNEL_CHECK();
+    GD_TRY(gd_tile_offsets(ctx, d_nl, T, &L));
     k_cp_pack_loops<<<T, 256, 0, ctx->stream>>>(d_cnt, d_nl, (const int*)(work + o_ls), (int*)(work + o_loops));
     GD_KERNEL_CHECK();
-    GD_TRY(gd_fetch(ctx, &L, d_nl + T, 8));
     GD_TRY(gd_fetch(ctx, task_vert_off, d_cnt, (size_t)(T + 1) * 8));
     GD_TRY(gd_fetch(ctx, task_loop_off, d_nl, (size_t)(T + 1) * 8));
     GD_TRY(gd_stream_sync(ctx));

@@ -194,7 +194,9 @@ __device__ __forceinline__ uint4 gload_u4(const void* p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
+// T: int, long long or double (the forms __shfl_down has)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, WAVE);
     return v;
@@ -210,14 +212,15 @@ __device__ __forceinline__ double wave_max(double v) {
     return v;
 }
 
-// Block-wide sum; result valid in thread 0.  `red` must hold blockDim.x/64 doubles.
-__device__ __forceinline__ double block_sum(double v, double* red) {
+// Block-wide sum; result valid in thread 0.  `red` must hold blockDim.x/64 values.
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
     v = wave_sum(v);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
     __syncthreads();
     if (lane == 0) red[wv] = v;
     __syncthreads();
-    double r = 0;
+    T r = 0;
     if (threadIdx.x == 0)
         for (int i = 0; i < nw; ++i) r += red[i];
     return r;

@@ -6,10 +6,10 @@
 // count pass and the write pass each regenerate it.  A generator that is not PCG64 draws on the host and the same two
 // kernels read the uploaded vector instead.
 //
-// Ordered compaction: a block owns a tile of DRAW_TILE consecutive rows and its threads walk it strided (lane-consecutive
-// rows: coalesced weight reads, one multiply-add of the 256-step map per row); pass 1 counts the kept rows of every tile,
-// one block scans the tile counts (tilescan.hpp), pass 2 recomputes the flags and writes each kept row at tile offset + rank inside the
-// tile (ballots per wave and item round).  The list comes out ascending, as np.nonzero gives it.
+// The row list is the ordered compaction of tilescan.hpp with DrawArgs as its predicate: a block owns a tile of DRAW_TILE
+// consecutive rows and its threads walk it strided (lane-consecutive rows: coalesced weight reads, one multiply-add of the
+// 256-step map per row), once in the count pass and once in the place pass.  The list comes out ascending, as np.nonzero
+// gives it.
 #include "ctx.hpp"
 #include "pcg64.hpp"
 #include "tilescan.hpp"
@@ -17,8 +17,9 @@
 #define DRAW_THREADS 256
 #define DRAW_ITEMS 8
 #define DRAW_TILE (DRAW_THREADS * DRAW_ITEMS)
-#define DRAW_WAVES (DRAW_THREADS / WAVE)
 
+namespace {
+// the predicate of the compaction (tilescan.hpp)
 struct DrawArgs {
     const double* w;     // sample weights, nullptr = unit weights
     const double* rand;  // N variates, nullptr = PCG64 from (state, inc)
@@ -27,72 +28,33 @@ struct DrawArgs {
     uint64_t a_hi, a_lo, c_hi, c_lo;              // gdpcg::stride(inc, DRAW_THREADS)
     double a, b;
     int mode;  // 0: w / (a * b)   1: (w / a) / b   -- the reference's two operation orders round differently
-};
 
-// bit q = this thread's row  tile * DRAW_TILE + q * DRAW_THREADS + threadIdx.x  is kept
-__device__ __forceinline__ unsigned draw_flags(const DrawArgs& p, int64_t tile) {
-    const double ab = p.a * p.b;
-    int64_t i = tile * DRAW_TILE + threadIdx.x;
-    gdpcg::u128 s = 0;
-    const gdpcg::Affine step = {gdpcg::make_u128(p.a_hi, p.a_lo), gdpcg::make_u128(p.c_hi, p.c_lo)};
-    if (!p.rand && i < p.N) {
-        gdpcg::Pcg64 g = {gdpcg::make_u128(p.state_hi, p.state_lo), gdpcg::make_u128(p.inc_hi, p.inc_lo)};
-        g.advance((gdpcg::u128)(uint64_t)(i + 1));  // draw i is the output of the state after i + 1 steps
-        s = g.state;
-    }
-    unsigned m = 0;
-#pragma unroll
-    for (int q = 0; q < DRAW_ITEMS; ++q, i += DRAW_THREADS) {
-        if (i < p.N) {
-            const double r = p.rand ? p.rand[i] : gdpcg::to_double(gdpcg::output(s));
-            const double w = p.w ? p.w[i] : 1.0;
-            const double thr = p.mode ? (w / p.a) / p.b : w / ab;
-            if (r <= thr) m |= 1u << q;
+    // bit q = this thread's row  tile * DRAW_TILE + q * DRAW_THREADS + threadIdx.x  is kept
+    __device__ __forceinline__ unsigned operator()(int64_t tile) const {
+        const double ab = a * b;
+        int64_t i = tile * DRAW_TILE + threadIdx.x;
+        gdpcg::u128 s = 0;
+        const gdpcg::Affine step = {gdpcg::make_u128(a_hi, a_lo), gdpcg::make_u128(c_hi, c_lo)};
+        if (!rand && i < N) {
+            gdpcg::Pcg64 g = {gdpcg::make_u128(state_hi, state_lo), gdpcg::make_u128(inc_hi, inc_lo)};
+            g.advance((gdpcg::u128)(uint64_t)(i + 1));  // draw i is the output of the state after i + 1 steps
+            s = g.state;
         }
-        s = step(s);
-    }
-    return m;
-}
-
-__global__ void __launch_bounds__(DRAW_THREADS) k_draw_count(DrawArgs p, long long* __restrict__ tile_cnt) {
-    __shared__ int red[DRAW_WAVES];
-    int c = __popc(draw_flags(p, blockIdx.x));
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, WAVE);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int i = 0; i < DRAW_WAVES; ++i) t += red[i];
-        tile_cnt[blockIdx.x] = t;
-    }
-}
-
-__global__ void __launch_bounds__(DRAW_THREADS) k_draw_write(DrawArgs p, const long long* __restrict__ tile_off,
-                                                              int32_t* __restrict__ rows, int64_t capacity) {
-    __shared__ int wc[DRAW_ITEMS][DRAW_WAVES];  // kept rows of (item round, wave): the tile's rows in ascending order
-    const unsigned m = draw_flags(p, blockIdx.x);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int before[DRAW_ITEMS];  // kept rows of this round in lower lanes of this wave
+        unsigned m = 0;
 #pragma unroll
-    for (int q = 0; q < DRAW_ITEMS; ++q) {
-        const unsigned long long bal = __ballot((m >> q) & 1u);
-        before[q] = __popcll(bal & ((1ULL << lane) - 1ULL));
-        if (lane == 0) wc[q][wv] = __popcll(bal);
-    }
-    __syncthreads();
-    long long pos = tile_off[blockIdx.x];
-    const int64_t i0 = (int64_t)blockIdx.x * DRAW_TILE + threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < DRAW_ITEMS; ++q) {
-        for (int v = 0; v < DRAW_WAVES; ++v) {
-            if (v == wv && ((m >> q) & 1u)) {
-                const long long at = pos + before[q];
-                if (at < capacity) rows[at] = (int32_t)(i0 + (int64_t)q * DRAW_THREADS);
+        for (int q = 0; q < DRAW_ITEMS; ++q, i += DRAW_THREADS) {
+            if (i < N) {
+                const double r = rand ? rand[i] : gdpcg::to_double(gdpcg::output(s));
+                const double wi = w ? w[i] : 1.0;
+                const double thr = mode ? (wi / a) / b : wi / ab;
+                if (r <= thr) m |= 1u << q;
             }
-            pos += wc[q][v];
+            s = step(s);
         }
+        return m;
     }
-}
+};
+}  // namespace
 
 // out[k * m + c] = column colidx[c] at row rows[k]; a row outside the sample set gives NaN (never an out-of-range read)
 __global__ void __launch_bounds__(256) k_gather_rows(const double* __restrict__ cols, int64_t ld, int64_t N,
@@ -132,12 +94,8 @@ int gd_draw_single_rows(gd_ctx* ctx, const uint64_t* pcg_state, const void* d_ra
         p.a_hi = gdpcg::hi64(step.a), p.a_lo = gdpcg::lo64(step.a), p.c_hi = gdpcg::hi64(step.c), p.c_lo = gdpcg::lo64(step.c);
     }
     p.a = a, p.b = b, p.mode = mode;
-    k_draw_count<<<nb, DRAW_THREADS, 0, ctx->stream>>>(p, cnt);
-    GD_KERNEL_CHECK();
-    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(cnt, nb);
-    GD_KERNEL_CHECK();
     long long total = 0;
-    GD_TRY(gd_fetch(ctx, &total, cnt + nb, 8));
+    GD_TRY((gd_compact_count<DRAW_THREADS, DRAW_ITEMS>(ctx, p, nb, cnt, &total)));
     GD_TRY(gd_stream_sync(ctx));
     *count_out = total;
     if (total > capacity) {
@@ -145,8 +103,7 @@ int gd_draw_single_rows(gd_ctx* ctx, const uint64_t* pcg_state, const void* d_ra
         return GD_DRAW_MORE_ROWS;
     }
     if (total == 0) return GD_OK;
-    k_draw_write<<<nb, DRAW_THREADS, 0, ctx->stream>>>(p, cnt, (int32_t*)d_rows, capacity);
-    GD_KERNEL_CHECK();
+    GD_TRY((gd_compact_place<DRAW_THREADS, DRAW_ITEMS>(ctx, p, nb, cnt, (int32_t*)d_rows, capacity)));
     GD_TRY(gd_stream_sync(ctx));
     return GD_OK;
 }

@@ -109,14 +109,8 @@ __global__ void __launch_bounds__(FMT_THREADS) k_format(FmtArgs p, long long* __
             fmt_decimal(valid ? fmt_load(p, k, j) : 0, valid, p.prec, ws_wave, &d);
             if (valid) bytes += gdfmt::text_length(d, p.width, p.prec) + fmt_tail(p, j);
         }
-        for (int o = 32; o > 0; o >>= 1) bytes += __shfl_down(bytes, o, WAVE);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bytes;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            long long t = 0;
-            for (int i = 0; i < FMT_WAVES; ++i) t += red[i];
-            tile_bytes[blockIdx.x] = t;
-        }
+        bytes = block_sum(bytes, red);
+        if (threadIdx.x == 0) tile_bytes[blockIdx.x] = bytes;
         return;
     }
 
@@ -213,10 +207,8 @@ static int format_common(gd_ctx* ctx, FmtArgs p, const int32_t* srcs_host, void*
     const size_t lds = (size_t)fmt_lds(p.TR, p.m, p.slot).total;
     k_format<false><<<nb, FMT_THREADS, FMT_COUNT_LDS, ctx->stream>>>(p, cnt, nullptr, 0);
     GD_KERNEL_CHECK();
-    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(cnt, nb);
-    GD_KERNEL_CHECK();
     long long total = 0;
-    GD_TRY(gd_fetch(ctx, &total, cnt + nb, 8));
+    GD_TRY(gd_tile_offsets(ctx, cnt, nb, &total));
     GD_TRY(gd_stream_sync(ctx));
     *bytes_out = total;
     if (total > capacity) {

@@ -443,9 +443,7 @@ static int scan_common(gd_ctx* ctx, ParseArgs& p, ScanOut* o) {
     q.m = 0;
     k_ingest<false><<<o->nb, ING_THREADS, ING_SCAN_LDS, ctx->stream>>>(q, o->cnt, o->d_res);
     GD_KERNEL_CHECK();
-    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(o->cnt, o->nb);
-    GD_KERNEL_CHECK();
-    GD_TRY(gd_fetch(ctx, &o->rows, o->cnt + o->nb, 8));
+    GD_TRY(gd_tile_offsets(ctx, o->cnt, o->nb, &o->rows));
     GD_TRY(gd_fetch(ctx, &o->res, o->d_res, sizeof(ParseRes)));
     GD_TRY(gd_stream_sync(ctx));
     if (o->res.flags) {

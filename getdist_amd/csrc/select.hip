@@ -2,9 +2,8 @@
 // thin, removeBurn, deleteFixedParams, addDerived, re-weighting) without the host's fancy indexing and the re-upload.
 //
 // gd_select_samples builds the new set beside the old one:
-//   row list   a mask or a weight threshold becomes an ascending int32 row list: k_sel_count counts the kept rows of every
-//              tile of GD_SEL_TILE rows, k_tile_scan turns the counts into offsets (and the total K), k_sel_place writes
-//              each tile's rows behind its offset, ranked inside a wave by ballot + popcount so the order is the rows'.
+//   row list   a mask or a weight threshold becomes an ascending int32 row list: the ordered compaction of tilescan.hpp
+//              over tiles of GD_SEL_TILE rows with SelKeep as its predicate (count, scan to offsets and the total K, place).
 //   gather     k_sel_gather: out[c][k] = in[col(c)][rows[k]].  A thread owns two consecutive k (one 16-byte store per
 //              column), keeps its two row numbers in registers and walks a chunk of GATHER_CH columns with all the chunk's
 //              loads in flight before the first store; grid (row tiles, column chunks).  For an ascending list the loads of
@@ -27,64 +26,24 @@ constexpr int kSelIters = GD_SEL_TILE / kSelThreads;  // rounds of a block over 
 constexpr int GATHER_CH = 8;                          // columns per block of the gather
 static_assert(GD_SEL_TILE % kSelThreads == 0, "a tile is a whole number of block rounds");
 
-// row i is kept: its mask byte is set (mask != nullptr), else its weight exceeds thr
-__device__ __forceinline__ bool sel_keep(const unsigned char* __restrict__ mask, const double* __restrict__ w, double thr, int64_t i) {
-    return mask ? mask[i] != 0 : w[i] > thr;
-}
+// the predicate of the compaction (tilescan.hpp): row i is kept when its mask byte is set (mask != nullptr), else when its
+// weight exceeds thr
+struct SelKeep {
+    const unsigned char* mask;
+    const double* w;
+    double thr;
+    int64_t N;
 
-__global__ void __launch_bounds__(kSelThreads)
-k_sel_count(const unsigned char* __restrict__ mask, const double* __restrict__ w, double thr, int64_t N, long long* __restrict__ cnt) {
-    __shared__ int wave_cnt[kSelThreads / WAVE];
-    const int64_t r0 = (int64_t)blockIdx.x * GD_SEL_TILE;
-    int c = 0;
+    __device__ __forceinline__ unsigned operator()(int64_t tile) const {
+        unsigned m = 0;
 #pragma unroll
-    for (int it = 0; it < kSelIters; ++it) {
-        const int64_t i = r0 + it * kSelThreads + threadIdx.x;
-        c += (i < N && sel_keep(mask, w, thr, i)) ? 1 : 0;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, WAVE);
-    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int k = 0; k < kSelThreads / WAVE; ++k) t += wave_cnt[k];
-        cnt[blockIdx.x] = t;
-    }
-}
-
-// off: the exclusive scan of the tile counts.  Every store lands below off[tile + 1] <= K <= N (the list holds N entries).
-__global__ void __launch_bounds__(kSelThreads)
-k_sel_place(const unsigned char* __restrict__ mask, const double* __restrict__ w, double thr, int64_t N,
-            const long long* __restrict__ off, int32_t* __restrict__ rows) {
-    __shared__ int wave_cnt[kSelIters][kSelThreads / WAVE];
-    const int64_t r0 = (int64_t)blockIdx.x * GD_SEL_TILE;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bool keep[kSelIters];
-    int rank[kSelIters];
-#pragma unroll
-    for (int it = 0; it < kSelIters; ++it) {
-        const int64_t i = r0 + it * kSelThreads + threadIdx.x;
-        keep[it] = i < N && sel_keep(mask, w, thr, i);
-        const unsigned long long b = __ballot(keep[it]);
-        rank[it] = __popcll(b & ((1ull << lane) - 1ull));  // kept rows of this wave's round below this lane
-        if (lane == 0) wave_cnt[it][wv] = __popcll(b);
-    }
-    __syncthreads();
-    long long base = off[blockIdx.x];
-#pragma unroll
-    for (int it = 0; it < kSelIters; ++it) {
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < kSelThreads / WAVE; ++k) {
-            const int v = wave_cnt[it][k];
-            before += (k < wv) ? v : 0;
-            total += v;
+        for (int q = 0; q < kSelIters; ++q) {
+            const int64_t i = tile * GD_SEL_TILE + q * kSelThreads + threadIdx.x;
+            if (i < N && (mask ? mask[i] != 0 : w[i] > thr)) m |= 1u << q;
         }
-        if (keep[it]) rows[base + before + rank[it]] = (int32_t)(r0 + it * kSelThreads + threadIdx.x);
-        base += total;
+        return m;
     }
-}
+};
 
 // out[c * ld_out + k] = in[col(c) * ld_in + rows[k]], col(c) = colmap[c] (colmap == nullptr: c), k < K, c < ncols.
 // out + c * ld_out is 16-byte aligned for every c (ld_out is a multiple of 512, the base a hipMalloc block).
@@ -138,15 +97,10 @@ struct Plan {
 
 // the device row list of a mask / threshold selection, in scratch2 from `d_rows` on; K comes back
 int build_row_list(gd_ctx* ctx, const unsigned char* d_mask, double thr, long long* d_cnt, int nb, int32_t* d_rows, int64_t* K_out) {
-    const int64_t N = ctx->N;
-    k_sel_count<<<nb, kSelThreads, 0, ctx->stream>>>(d_mask, ctx->w, thr, N, d_cnt);
-    GD_KERNEL_CHECK();
-    k_tile_scan<<<1, 1024, 0, ctx->stream>>>(d_cnt, nb);
-    GD_KERNEL_CHECK();
-    k_sel_place<<<nb, kSelThreads, 0, ctx->stream>>>(d_mask, ctx->w, thr, N, d_cnt, d_rows);
-    GD_KERNEL_CHECK();
+    const SelKeep keep = {d_mask, ctx->w, thr, ctx->N};
     long long total = 0;
-    GD_TRY(gd_fetch(ctx, &total, d_cnt + nb, 8));
+    GD_TRY((gd_compact_count<kSelThreads, kSelIters>(ctx, keep, nb, d_cnt, &total)));
+    GD_TRY((gd_compact_place<kSelThreads, kSelIters>(ctx, keep, nb, d_cnt, d_rows, ctx->N)));  // the list holds N entries
     GD_TRY(gd_stream_sync(ctx));
     *K_out = total;
     return GD_OK;

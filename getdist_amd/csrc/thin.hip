@@ -6,6 +6,7 @@
 // its first output position is  C_{i-1}/f  -- so ONE prefix sum of the weights (cached per sample set) turns every
 // later thinning, for any factor and any chain [lo,hi), into an embarrassingly parallel scatter.
 #include "ctx.hpp"
+#include "tilescan.hpp"
 
 #define SCAN_THREADS 256
 #define SCAN_ITEMS 8
@@ -22,41 +23,11 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_wscan_reduce(const double* __r
         const int64_t i = base + (int64_t)q * SCAN_THREADS + threadIdx.x;
         if (i < N) s += w_int(w, i);
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, WAVE);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int i = 0; i < SCAN_THREADS / 64; ++i) t += red[i];
-        bsum[blockIdx.x] = t;
-    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = s;
 }
 
-// exclusive scan of the tile sums, one block
-__global__ void __launch_bounds__(1024) k_wscan_blocks(long long* __restrict__ bsum, int nb) {
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < nb; c0 += 1024) {
-        const int i = c0 + threadIdx.x;
-        const long long v = (i < nb) ? bsum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const long long a = (threadIdx.x >= (unsigned)o) ? sh[threadIdx.x - o] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (i < nb) bsum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-}
-
-// inclusive cumulative weights: each thread owns SCAN_ITEMS consecutive rows of its tile
+// inclusive cumulative weights: each thread owns SCAN_ITEMS consecutive rows of its tile; boff: the scanned tile sums
 __global__ void __launch_bounds__(SCAN_THREADS) k_wscan_down(const double* __restrict__ w, int64_t N,
                                                               const long long* __restrict__ boff,
                                                               long long* __restrict__ C) {
@@ -164,16 +135,16 @@ static int ensure_weight_cumsum(gd_ctx* ctx) {
     const int nb = (int)((N + SCAN_TILE - 1) / SCAN_TILE);
     long long* C = nullptr;
     GD_HIP(hipMalloc((void**)&C, (size_t)(N * 8)));
-    long long* bsum = (long long*)gd_scratch(ctx, (int64_t)nb * 8);
+    long long* bsum = (long long*)gd_scratch(ctx, ((int64_t)nb + 1) * 8);  // the scan leaves the total behind the offsets
     if (!bsum) {
         (void)hipFree(C);
         return GD_ERR_NOMEM;
     }
     const double* w = ctx->w_sel ? ctx->w_main : ctx->w;  // always the sample weights
     k_wscan_reduce<<<nb, SCAN_THREADS, 0, ctx->stream>>>(w, N, bsum);
-    k_wscan_blocks<<<1, 1024, 0, ctx->stream>>>(bsum, nb);
+    const int scanned = gd_tile_offsets(ctx, bsum, nb, nullptr);
     k_wscan_down<<<nb, SCAN_THREADS, 0, ctx->stream>>>(w, N, bsum, C);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    if (scanned != GD_OK || hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
         (void)hipFree(C);
         return gd_fail(ctx, GD_ERR_HIP, "cumulative-weight scan failed");
     }

@@ -690,23 +690,21 @@ class MCSamples(Chains):
             mx, mn = np.max(w), np.min(w)  # chains.py:1017-1027
             if mn < mx * self.min_weight_ratio:
                 thr = mx * self.min_weight_ratio
-                if self._device_edit_applies() and np.any(w > thr):
+                keep = w > thr
+                on_device = self._device_edit_applies() and np.any(keep)
+                if on_device:
                     # the whole array goes up as it is and the rows are dropped there (GD_SEL_WEIGHT_GT, the same comparison
                     # on the resident weights): no fancy-indexed copy of the matrix on the host
                     self.ctx.upload(self.samples, w)
-                    if self._select_on_device(rows=("weight_gt", thr)):
-                        keep = w > thr
-                        self.weights = w[keep]
-                        if self.loglikes is not None:
-                            self.loglikes = self.loglikes[keep]
-                        self.numrows = self.ctx.N
-                        return
-                keep = w > thr
-                self.samples = self.samples[keep]
+                    on_device = self._select_on_device(rows=("weight_gt", thr))
+                if not on_device:
+                    self.samples = self.samples[keep]
                 self.weights = w = w[keep]
                 if self.loglikes is not None:
                     self.loglikes = self.loglikes[keep]
-                self.numrows = self.samples.shape[0]
+                self.numrows = len(w)
+                if on_device:
+                    return
         share = getattr(self, "_column_share", None)
         if share is not None:
             share.upload(self.ctx, self.samples, w)  # (collective: every rank of the job uploads at the same point)
