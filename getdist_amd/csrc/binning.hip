@@ -716,7 +716,7 @@ __global__ void __launch_bounds__(256) k_prebin_fix(const PrebinColB* __restrict
 
 // Host side of the bucket route: which of the requested columns have valid bucket columns, their records, and the launches.
 // `which[c]` = slot among the bucket-route columns or -1.  Everything is enqueued on ctx->stream; the records and tables
-// live in `base` (device scratch the caller reserved: bucket_route_bytes()).
+// live in device scratch the caller reserved (BucketRouteLayout).
 struct BucketRoute {
     std::vector<PrebinColB> recs;
     std::vector<int> slot_of;  // per requested column
@@ -779,31 +779,38 @@ static BucketShape bucket_shape(const gd_ctx* ctx, int nc) {
         if (atoi(e) > 0 && atoi(e) < S.cap) S.cap = atoi(e);
     return S;
 }
-static int64_t bucket_route_bytes(const gd_ctx* ctx, const BucketRoute& R) {
-    if (R.recs.empty()) return 0;
-    const int nc = (int)R.recs.size();
-    const BucketShape S = bucket_shape(ctx, nc);
-    return ((int64_t)nc * sizeof(PrebinColB) + 255) / 256 * 256 + ((int64_t)nc * R.nbmax * 2 + 255) / 256 * 256 +
-           ((int64_t)nc * 8 + 255) / 256 * 256 + ((int64_t)nc * S.nblk * 4 + 255) / 256 * 256 + (int64_t)nc * S.nblk * S.cap * 4 + 256;
-}
+// The scratch layout of the bucket route (empty when no column takes it): callers size their block with sp.bytes() and
+// say where the route's part of it starts with sp.place(), or obtain a block of its own with sp.get2().
+struct BucketRouteLayout {
+    ScratchPlan sp;
+    BucketShape S{};
+    ScratchPlan::Buf<PrebinColB> recs;
+    ScratchPlan::Buf<unsigned short> lut;
+    ScratchPlan::Buf<unsigned long long> bad;
+    ScratchPlan::Buf<int> cnt;
+    ScratchPlan::Buf<unsigned int> list;
+    BucketRouteLayout(const gd_ctx* ctx, const BucketRoute& R) {
+        if (R.recs.empty()) return;
+        const int nc = (int)R.recs.size();
+        S = bucket_shape(ctx, nc);
+        recs = sp.take<PrebinColB>(nc);
+        lut = sp.take<unsigned short>((int64_t)nc * R.nbmax);
+        bad = sp.take<unsigned long long>(nc);
+        cnt = sp.take<int>((int64_t)nc * S.nblk);
+        list = sp.tail<unsigned int>((int64_t)nc * S.nblk * S.cap);
+        sp.pad(256);
+    }
+};
 // the out-of-range counters (R.recs.size() of them, zeroed here) come back through bad_dev
 template <bool OUT8>
-static int bucket_route_launch(gd_ctx* ctx, const BucketRoute& R, char* base, int F, unsigned long long** bad_dev) {
+static int bucket_route_launch(gd_ctx* ctx, const BucketRoute& R, const BucketRouteLayout& L, int F, unsigned long long** bad_dev) {
     const int nc = (int)R.recs.size();
-    const BucketShape S = bucket_shape(ctx, nc);
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_recs = take((int64_t)nc * sizeof(PrebinColB)), o_lut = take((int64_t)nc * R.nbmax * 2), o_bad = take((int64_t)nc * 8),
-                  o_cnt = take((int64_t)nc * S.nblk * 4), o_list = take((int64_t)nc * S.nblk * S.cap * 4);
-    PrebinColB* d_recs = (PrebinColB*)(base + o_recs);
-    unsigned short* d_lut = (unsigned short*)(base + o_lut);
-    unsigned long long* d_bad = (unsigned long long*)(base + o_bad);
-    int* d_cnt = (int*)(base + o_cnt);
-    unsigned int* d_list = (unsigned int*)(base + o_list);
+    const BucketShape S = L.S;
+    PrebinColB* d_recs = L.recs;
+    unsigned short* d_lut = L.lut;
+    unsigned long long* d_bad = L.bad;
+    int* d_cnt = L.cnt;
+    unsigned int* d_list = L.list;
     GD_TRY(gd_h2d(ctx, d_recs, R.recs.data(), (size_t)nc * sizeof(PrebinColB)));
     GD_HIP(hipMemsetAsync(d_bad, 0, (size_t)nc * 8, ctx->stream));
     k_bucket_lut<<<dim3(R.nbmax / 256, nc), 256, 0, ctx->stream>>>(d_recs, F, R.nbmax, d_lut);
@@ -1144,19 +1151,11 @@ static int launch_hist2d_p16(gd_ctx* ctx, int B, const std::vector<Hist2DPair>& 
     }
     const int units = (B * nchunks + 7) / 8 * 8;
     const int64_t nblocks = (int64_t)units * nstripes;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_pairs = take((int64_t)B * sizeof(Hist2DPair)), o_flags = take((int64_t)B * 4),
-                  o_part = take((int64_t)B * nchunks * nstripes * nwords * 4);
-    char* base = (char*)gd_scratch2(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    Hist2DPair* d_pairs = (Hist2DPair*)(base + o_pairs);
-    int* d_flags = (int*)(base + o_flags);
-    unsigned int* d_part = (unsigned int*)(base + o_part);
+    ScratchPlan sp;
+    auto d_pairs = sp.take<Hist2DPair>(B);
+    auto d_flags = sp.take<int>(B);
+    auto d_part = sp.take<unsigned int>((int64_t)B * nchunks * nstripes * nwords);
+    GD_TRY(sp.get2(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
     GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
     GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_f64_p16<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
@@ -1235,35 +1234,26 @@ static int hist1d_core(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const do
     GD_REQUIRE(ctx && cols && binmin && width && out && ncols > 0, "bad argument");
     GD_REQUIRE(F >= 2 && F <= 4096, "fine_bins out of range (2..4096)");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
-    for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_COLUMNS(cols, ncols);
     const int nblk = ctx->cu_count;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_part = take((int64_t)ncols * nblk * F * 8), o_out = take((int64_t)ncols * F * 8),
-                  o_idx = take((int64_t)ncols * 4), o_b = take((int64_t)ncols * 8), o_w = take((int64_t)ncols * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    double* d_part = (double*)(base + o_part);
-    double* d_out = out_on_device ? out : (double*)(base + o_out);
-    int32_t* d_idx = (int32_t*)(base + o_idx);
-    double* d_b = (double*)(base + o_b);
-    double* d_w = (double*)(base + o_w);
+    ScratchPlan sp;
+    auto d_part = sp.take<double>((int64_t)ncols * nblk * F);
+    auto b_out = sp.take<double>((int64_t)ncols * F);
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_b = sp.take<double>(ncols);
+    auto d_w = sp.take<double>(ncols);
+    GD_TRY(sp.get(ctx));
+    double* d_out = out_on_device ? out : b_out.ptr();
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
     GD_TRY(gd_h2d(ctx, d_b, binmin, (size_t)ncols * 8));
     GD_TRY(gd_h2d(ctx, d_w, width, (size_t)ncols * 8));
     dim3 grid(nblk, ncols);
     const size_t lds = (size_t)4 * F * 8;
-    if (ctx->w) {
-        GD_HIP(hipFuncSetAttribute((const void*)k_hist1d<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 8));
-        k_hist1d<true><<<grid, 256, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_b, d_w, F, d_part);
-    } else {
-        GD_HIP(hipFuncSetAttribute((const void*)k_hist1d<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 8));
-        k_hist1d<false><<<grid, 256, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, ctx->N, d_b, d_w, F, d_part);
-    }
+    GD_TRY(gd_by_flag(ctx->w != nullptr, [&](auto HW) -> int {
+        GD_HIP(hipFuncSetAttribute((const void*)k_hist1d<HW.value>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4096 * 8));
+        k_hist1d<HW.value><<<grid, 256, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_b, d_w, F, d_part);
+        return GD_OK;
+    }));
     GD_KERNEL_CHECK();
     k_hist1d_reduce<<<dim3((F + 255) / 256, ncols), 256, 0, ctx->stream>>>(d_part, nblk, F, d_out);
     GD_KERNEL_CHECK();
@@ -1286,16 +1276,15 @@ int gd_bin_indices(gd_ctx* ctx, int32_t col, double binmin, double width, int32_
                    int32_t* idx_out, int64_t* n_out_of_range) {
     GD_REQUIRE(ctx && idx_out, "bad argument");
     GD_REQUIRE(ctx->cols && col >= 0 && col < ctx->n + GD_EXTRA_COLS, "bad column");
-    char* base = (char*)gd_scratch(ctx, ctx->N * 4 + 256);
-    if (!base) return GD_ERR_NOMEM;
-    unsigned long long* d_bad = (unsigned long long*)base;
-    int32_t* d_idx = (int32_t*)(base + 256);
+    ScratchPlan sp;
+    auto d_bad = sp.take<unsigned long long>(1);
+    auto d_idx = sp.tail<int32_t>(ctx->N);
+    GD_TRY(sp.get(ctx));
     GD_HIP(hipMemsetAsync(d_bad, 0, 8, ctx->stream));
     const double* x = ctx->cols + (int64_t)col * ctx->ld;
-    if (round_half)
-        k_bin_indices<true, int32_t><<<4 * ctx->cu_count, 256, 0, ctx->stream>>>(x, ctx->N, binmin, width, F, d_idx, d_bad);
-    else
-        k_bin_indices<false, int32_t><<<4 * ctx->cu_count, 256, 0, ctx->stream>>>(x, ctx->N, binmin, width, F, d_idx, d_bad);
+    gd_by_flag(round_half != 0, [&](auto ROUND) {
+        k_bin_indices<ROUND.value, int32_t><<<4 * ctx->cu_count, 256, 0, ctx->stream>>>(x, ctx->N, binmin, width, F, d_idx, d_bad);
+    });
     GD_KERNEL_CHECK();
     unsigned long long bad = 0;
     GD_TRY(gd_fetch(ctx, idx_out, d_idx, (size_t)ctx->N * 4));
@@ -1313,10 +1302,10 @@ int gd_prebin(gd_ctx* ctx, int32_t col, double binmin, double width, int32_t F, 
         void* const idx1[1] = {d_idx_u16};
         const BucketRoute R = bucket_route(ctx, &col, 1, &binmin, &width, idx1);
         if (!R.recs.empty()) {  // from the column's 2-byte buckets (stream-ordered like the kernel below: no wait here)
-            char* base = (char*)gd_scratch2(ctx, bucket_route_bytes(ctx, R));
-            if (!base) return GD_ERR_NOMEM;
+            BucketRouteLayout L(ctx, R);
+            GD_TRY(L.sp.get2(ctx));
             unsigned long long* unused = nullptr;
-            return bucket_route_launch<false>(ctx, R, base, F, &unused);
+            return bucket_route_launch<false>(ctx, R, L, F, &unused);
         }
     }
     const double* x = ctx->cols + (int64_t)col * ctx->ld;
@@ -1344,10 +1333,12 @@ int gd_prebin_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doubl
         hc.push_back(r);
     }
     const int nfp = (int)hc.size();
-    const int64_t o_route = ((int64_t)nfp * sizeof(PrebinCol) + 255) / 256 * 256;
-    char* base = (char*)gd_scratch2(ctx, o_route + bucket_route_bytes(ctx, R));
-    if (!base) return GD_ERR_NOMEM;
-    PrebinCol* d_c = (PrebinCol*)base;
+    BucketRouteLayout L(ctx, R);
+    ScratchPlan sp;
+    auto d_c = sp.take<PrebinCol>(nfp);
+    auto d_route = sp.tail<char>(L.sp.bytes());
+    GD_TRY(sp.get2(ctx));
+    L.sp.place(d_route);
     if (nfp) {
         GD_TRY(gd_h2d(ctx, d_c, hc.data(), (size_t)nfp * sizeof(PrebinCol)));
         int nblk = (int)((ctx->N / 8 + 255) / 256);  // one 8-sample iteration per thread at most, like the single-column kernel
@@ -1358,7 +1349,7 @@ int gd_prebin_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doubl
     }
     if (!R.recs.empty()) {
         unsigned long long* unused = nullptr;
-        GD_TRY(bucket_route_launch<false>(ctx, R, base + o_route, F, &unused));
+        GD_TRY(bucket_route_launch<false>(ctx, R, L, F, &unused));
     }
     GD_TRY(gd_stream_sync(ctx));  // hc / d_c lifetime
     return GD_OK;
@@ -1387,23 +1378,18 @@ static int launch_hist2d_u16(gd_ctx* ctx, int B, const std::vector<Hist2DPair>& 
     const int nstripes = (F + R - 1) / R;
     const int units = (B + 7) / 8 * 8;
     const int64_t nblocks = (int64_t)units * nstripes;
-    const int64_t o_flags = ((int64_t)B * sizeof(Hist2DPair) + 255) / 256 * 256;
-    char* base = (char*)gd_scratch2(ctx, o_flags + (int64_t)B * 4);
-    if (!base) return GD_ERR_NOMEM;
-    Hist2DPair* d_pairs = (Hist2DPair*)base;
-    int* d_flags = (int*)(base + o_flags);
+    ScratchPlan sp;
+    auto d_pairs = sp.take<Hist2DPair>(B);
+    auto d_flags = sp.tail<int>(B);
+    GD_TRY(sp.get2(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
     GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
     const size_t lds = ((size_t)R * F + 1) / 2 * 4;
-    if (ctx->w8) {
-        GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-        k_hist2d_u16<true><<<(unsigned)nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->N, F, R, nstripes, ctx->w8, d_hist,
-                                                                         d_flags);
-    } else {
-        GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-        k_hist2d_u16<false><<<(unsigned)nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->N, F, R, nstripes, nullptr, d_hist,
-                                                                          d_flags);
-    }
+    GD_TRY(gd_by_flag(ctx->w8 != nullptr, [&](auto HW8) -> int {
+        GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u16<HW8.value>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
+        k_hist2d_u16<HW8.value><<<(unsigned)nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->N, F, R, nstripes, ctx->w8, d_hist, d_flags);
+        return GD_OK;
+    }));
     GD_KERNEL_CHECK();
     std::vector<int> hf((size_t)B);
     GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
@@ -1439,12 +1425,11 @@ int gd_hist2d_prebinned(gd_ctx* ctx, int32_t B, const void* const* d_idx_x, cons
             const int units = (B * nchunks + 7) / 8 * 8;
             const int64_t nblocks = (int64_t)units * nstripes;
             const int nwords = (R * F + 1) / 2;
-            const int64_t o_flags = ((int64_t)B * sizeof(Hist2DPair) + 255) / 256 * 256, o_part = o_flags + ((int64_t)B * 4 + 255) / 256 * 256;
-            char* base = (char*)gd_scratch2(ctx, o_part + (int64_t)B * nchunks * nstripes * nwords * 4);
-            if (!base) return GD_ERR_NOMEM;
-            Hist2DPair* d_pairs = (Hist2DPair*)base;
-            int* d_flags = (int*)(base + o_flags);
-            unsigned int* d_part = (unsigned int*)(base + o_part);
+            ScratchPlan sp;
+            auto d_pairs = sp.take<Hist2DPair>(B);
+            auto d_flags = sp.take<int>(B);
+            auto d_part = sp.tail<unsigned int>((int64_t)B * nchunks * nstripes * nwords);
+            GD_TRY(sp.get2(ctx));
             GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
             GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
             GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u16_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
@@ -1530,12 +1515,13 @@ int gd_prebin8_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doub
         hc.push_back(r);
     }
     const int nfp = (int)hc.size();
-    const int64_t o_bad = ((int64_t)nfp * sizeof(PrebinCol8) + 255) / 256 * 256;
-    const int64_t o_route = o_bad + ((int64_t)nfp * 8 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch2(ctx, o_route + bucket_route_bytes(ctx, R));
-    if (!base) return GD_ERR_NOMEM;
-    PrebinCol8* d_c = (PrebinCol8*)base;
-    unsigned long long* d_bad = (unsigned long long*)(base + o_bad);
+    BucketRouteLayout L(ctx, R);
+    ScratchPlan sp;
+    auto d_c = sp.take<PrebinCol8>(nfp);
+    auto d_bad = sp.take<unsigned long long>(nfp);
+    auto d_route = sp.tail<char>(L.sp.bytes());
+    GD_TRY(sp.get2(ctx));
+    L.sp.place(d_route);
     if (nfp) {
         GD_TRY(gd_h2d(ctx, d_c, hc.data(), (size_t)nfp * sizeof(PrebinCol8)));
         GD_HIP(hipMemsetAsync(d_bad, 0, (size_t)nfp * 8, ctx->stream));
@@ -1546,7 +1532,7 @@ int gd_prebin8_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doub
         GD_KERNEL_CHECK();
     }
     unsigned long long* d_bad_bq = nullptr;
-    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, base + o_route, F, &d_bad_bq));
+    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, L, F, &d_bad_bq));
     std::vector<unsigned long long> hb((size_t)nfp), hq(R.recs.size());
     if (nfp) GD_TRY(gd_fetch(ctx, hb.data(), d_bad, (size_t)nfp * 8));
     if (!R.recs.empty()) GD_TRY(gd_fetch(ctx, hq.data(), d_bad_bq, hq.size() * 8));
@@ -1866,48 +1852,38 @@ static int hist2d_weighted_sorted(gd_ctx* ctx, int B, const void* const* d_idx_x
         std::vector<WKey> hk((size_t)nk);
         std::vector<WX> hx;
         std::vector<const unsigned char*> ixp((size_t)B, nullptr);
-        int64_t off = 0;
-        auto take = [&](int64_t nbytes) {
-            int64_t o = off;
-            off += (nbytes + 255) / 256 * 256;
-            return o;
-        };
-        const int64_t o_keys = take((int64_t)nk * sizeof(WKey)), o_xs = take((int64_t)npairs * sizeof(WX)),
-                      o_counts = take((int64_t)nk * ntiles * WS * 4), o_offsets = take((int64_t)nk * ntiles * WS * 8),
-                      o_starts = take((int64_t)nk * (WS + 1) * 8), o_ixp = take((int64_t)B * 8),
-                      o_units = take((int64_t)units.size() * sizeof(WUnit));
-        std::vector<int64_t> o_ij((size_t)nk), o_wq((size_t)nk);
-        std::vector<int64_t> o_ix;
-        for (int k = 0; k < nk; ++k) o_ij[k] = take(npad_max), o_wq[k] = take(npad_max * 8);
+        ScratchPlan sp;
+        auto d_keys = sp.take<WKey>(nk);
+        auto d_xs = sp.take<WX>(npairs);
+        auto d_counts = sp.take<int>((int64_t)nk * ntiles * WS);
+        auto d_offsets = sp.take<int64_t>((int64_t)nk * ntiles * WS);
+        auto d_starts = sp.take<int64_t>((int64_t)nk * (WS + 1));
+        auto d_ixp = sp.take<const unsigned char*>(B);
+        auto d_units = sp.take<WUnit>((int64_t)units.size());
+        std::vector<ScratchPlan::Buf<unsigned char>> d_ij((size_t)nk), d_ix;
+        std::vector<ScratchPlan::Buf<unsigned long long>> d_wq((size_t)nk);
+        for (int k = 0; k < nk; ++k) d_ij[k] = sp.take<unsigned char>(npad_max), d_wq[k] = sp.take<unsigned long long>(npad_max);
         for (int k = 0; k < nk; ++k)
-            for (size_t q = 0; q < by_key[key_order[k0 + k]].size(); ++q) o_ix.push_back(take(npad_max));
-        char* base = (char*)gd_scratch2(ctx, off);
-        if (!base) return GD_ERR_NOMEM;
+            for (size_t q = 0; q < by_key[key_order[k0 + k]].size(); ++q) d_ix.push_back(sp.take<unsigned char>(npad_max));
+        GD_TRY(sp.get2(ctx));
         int xi = 0;
         for (int k = 0; k < nk; ++k) {
             const std::vector<int>& prs = by_key[key_order[k0 + k]];
             WKey& K = hk[k];
             K.iy = (const unsigned char*)key_order[k0 + k];
-            K.ij_perm = (unsigned char*)(base + o_ij[k]);
-            K.wq_perm = (unsigned long long*)(base + o_wq[k]);
+            K.ij_perm = d_ij[k];
+            K.wq_perm = d_wq[k];
             K.npad = npad_max;
             K.x_first = xi, K.x_count = (int)prs.size();
             for (int b : prs) {
                 WX X;
                 X.ix = (const unsigned char*)d_idx_x[b];
-                X.ix_perm = (unsigned char*)(base + o_ix[xi]);
+                X.ix_perm = d_ix[xi];
                 ixp[b] = X.ix_perm;
                 hx.push_back(X);
                 ++xi;
             }
         }
-        WKey* d_keys = (WKey*)(base + o_keys);
-        WX* d_xs = (WX*)(base + o_xs);
-        int* d_counts = (int*)(base + o_counts);
-        int64_t* d_offsets = (int64_t*)(base + o_offsets);
-        int64_t* d_starts = (int64_t*)(base + o_starts);
-        const unsigned char** d_ixp = (const unsigned char**)(base + o_ixp);
-        WUnit* d_units = (WUnit*)(base + o_units);
         GD_TRY(gd_h2d(ctx, d_keys, hk.data(), hk.size() * sizeof(WKey)));
         GD_TRY(gd_h2d(ctx, d_xs, hx.data(), hx.size() * sizeof(WX)));
         GD_TRY(gd_h2d(ctx, d_ixp, ixp.data(), ixp.size() * 8));
@@ -1944,20 +1920,19 @@ int gd_hist2d_prebinned8(gd_ctx* ctx, int32_t B, const void* const* d_idx_x, con
         GD_REQUIRE(hp[b].ix && hp[b].iy, "null index column");
     }
     const int nchunks = u8_chunks(ctx, B, ctx->N);
-    const int64_t o_flags = ((int64_t)B * sizeof(Hist2DPair8) + 255) / 256 * 256, o_part = o_flags + ((int64_t)B * 4 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch2(ctx, o_part + (nchunks > 1 ? (int64_t)B * nchunks * 32768 * 4 : 0));
-    if (!base) return GD_ERR_NOMEM;
-    Hist2DPair8* d_pairs = (Hist2DPair8*)base;
-    int* d_flags = (int*)(base + o_flags);
+    ScratchPlan sp;
+    auto d_pairs = sp.take<Hist2DPair8>(B);
+    auto d_flags = sp.take<int>(B);
+    auto d_part = sp.tail<unsigned int>(nchunks > 1 ? (int64_t)B * nchunks * 32768 : 0);
+    GD_TRY(sp.get2(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair8)));
     GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
     const int nblocks = (B * nchunks + 7) / 8 * 8;
     GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u8_pf<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES + 128));
-    k_hist2d_u8_pf<3><<<nblocks, 1024, LDS_HIST_BYTES + 128, ctx->stream>>>(d_pairs, B, ctx->N, (double*)d_hist, d_flags, nchunks,
-                                                                              (unsigned int*)(base + o_part));
+    k_hist2d_u8_pf<3><<<nblocks, 1024, LDS_HIST_BYTES + 128, ctx->stream>>>(d_pairs, B, ctx->N, (double*)d_hist, d_flags, nchunks, d_part);
     GD_KERNEL_CHECK();
     if (nchunks > 1) {
-        k_p8_reduce<<<dim3(32, B), 256, 0, ctx->stream>>>((const unsigned int*)(base + o_part), nchunks, (double*)d_hist);
+        k_p8_reduce<<<dim3(32, B), 256, 0, ctx->stream>>>(d_part, nchunks, (double*)d_hist);
         GD_KERNEL_CHECK();
     }
     std::vector<int> hf((size_t)B);
@@ -2009,53 +1984,48 @@ int gd_prebin8_hist2d(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const dou
         hp[b].iy = (const unsigned char*)d_idx_y[b];
         GD_REQUIRE(hp[b].ix && hp[b].iy, "null index column");
     }
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_cols = take((int64_t)nfp * sizeof(PrebinCol8)), o_pairs = take((int64_t)B * sizeof(Hist2DPair8));
-    const int64_t table_bytes = off;
-    const int64_t o_bad = take((int64_t)nfp * 8), o_flags = take((int64_t)B * 4);
-    const int64_t zero_end = off;
+    BucketRouteLayout L(ctx, R);
+    ScratchPlan sp;
+    auto d_c = sp.take<PrebinCol8>(nfp);
+    auto d_pairs = sp.take<Hist2DPair8>(B);
+    const int64_t table_bytes = sp.bytes();  // the two tables go up in one copy
+    auto d_bad = sp.take<unsigned long long>(nfp);
+    auto d_flags = sp.take<int>(B);
+    const int64_t zero_end = sp.bytes();  // the counters and the flags are zeroed in one fill
     const int nchunks = u8_chunks(ctx, B, ctx->N);
-    const int64_t o_part = take(nchunks > 1 ? (int64_t)B * nchunks * 32768 * 4 : 0);
-    const int64_t o_route = take(bucket_route_bytes(ctx, R));
-    char* base = (char*)gd_scratch2(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
+    auto d_part = sp.take<unsigned int>(nchunks > 1 ? (int64_t)B * nchunks * 32768 : 0);
+    auto d_route = sp.take<char>(L.sp.bytes());
+    GD_TRY(sp.get2(ctx));
+    L.sp.place(d_route);
     {
         std::vector<char> tab((size_t)table_bytes, 0);
-        if (nfp) memcpy(tab.data() + o_cols, hc.data(), (size_t)nfp * sizeof(PrebinCol8));
-        memcpy(tab.data() + o_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair8));
-        GD_TRY(gd_stage_h2d(ctx, base, tab.data(), (size_t)table_bytes));
+        if (nfp) memcpy(tab.data() + d_c.off, hc.data(), (size_t)nfp * sizeof(PrebinCol8));
+        memcpy(tab.data() + d_pairs.off, hp.data(), (size_t)B * sizeof(Hist2DPair8));
+        GD_TRY(gd_stage_h2d(ctx, d_c, tab.data(), (size_t)table_bytes));
     }
-    GD_HIP(hipMemsetAsync(base + o_bad, 0, (size_t)(zero_end - o_bad), ctx->stream));
+    GD_HIP(hipMemsetAsync(d_bad, 0, (size_t)(zero_end - d_bad.off), ctx->stream));
     if (nfp) {
         int nblk = (int)((ctx->N / 8 + 255) / 256);
         if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
         if (nblk < 1) nblk = 1;
-        k_prebin8_batch<<<dim3(nblk, nfp), 256, 0, ctx->stream>>>((const PrebinCol8*)(base + o_cols), ctx->N, F,
-                                                                 (unsigned long long*)(base + o_bad));
+        k_prebin8_batch<<<dim3(nblk, nfp), 256, 0, ctx->stream>>>(d_c, ctx->N, F, d_bad);
         GD_KERNEL_CHECK();
     }
     unsigned long long* d_bad_bq = nullptr;
-    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, base + o_route, F, &d_bad_bq));
+    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, L, F, &d_bad_bq));
     const int nblocks = (B * nchunks + 7) / 8 * 8;
     GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u8_pf<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES + 128));
-    k_hist2d_u8_pf<3><<<nblocks, 1024, LDS_HIST_BYTES + 128, ctx->stream>>>((const Hist2DPair8*)(base + o_pairs), B, ctx->N,
-                                                                            (double*)d_hist, (int*)(base + o_flags), nchunks,
-                                                                            (unsigned int*)(base + o_part));
+    k_hist2d_u8_pf<3><<<nblocks, 1024, LDS_HIST_BYTES + 128, ctx->stream>>>(d_pairs, B, ctx->N, (double*)d_hist, d_flags, nchunks, d_part);
     GD_KERNEL_CHECK();
     if (nchunks > 1) {
-        k_p8_reduce<<<dim3(32, B), 256, 0, ctx->stream>>>((const unsigned int*)(base + o_part), nchunks, (double*)d_hist);
+        k_p8_reduce<<<dim3(32, B), 256, 0, ctx->stream>>>(d_part, nchunks, (double*)d_hist);
         GD_KERNEL_CHECK();
     }
     std::vector<unsigned long long> hb((size_t)nfp), hq(R.recs.size());
     std::vector<int> hf((size_t)B);
-    if (nfp) GD_TRY(gd_fetch(ctx, hb.data(), base + o_bad, (size_t)nfp * 8));
+    if (nfp) GD_TRY(gd_fetch(ctx, hb.data(), d_bad, (size_t)nfp * 8));
     if (!R.recs.empty()) GD_TRY(gd_fetch(ctx, hq.data(), d_bad_bq, hq.size() * 8));
-    GD_TRY(gd_fetch(ctx, hf.data(), base + o_flags, (size_t)B * 4));
+    GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
     GD_TRY(gd_stream_sync(ctx));
     int64_t nbad = 0;
     for (int c = 0; c < ncols; ++c) bad_out[c] = (int64_t)(R.slot_of[c] >= 0 ? hq[R.slot_of[c]] : hb[fp_of[c]]), nbad += bad_out[c];
@@ -2142,16 +2112,16 @@ int gd_minmax_affine(gd_ctx* ctx, int32_t B, const int32_t* coli, const int32_t*
         int nblk = (6 * ctx->cu_count + ng - 1) / ng;
         if (nblk < 8) nblk = 8;
         if (nblk > 1024) nblk = 1024;
-        const int64_t o_part = ((int64_t)ng * sizeof(MinmaxGroup) + 255) / 256 * 256;
         const int64_t part_doubles = (int64_t)ng * nblk * MMG_PAIRS * 2;
-        char* base = (char*)gd_scratch(ctx, o_part + part_doubles * 8);
-        if (!base) return GD_ERR_NOMEM;
-        GD_TRY(gd_h2d(ctx, base, groups.data(), (size_t)ng * sizeof(MinmaxGroup)));
-        k_minmax_affine_grouped<<<dim3(nblk, ng), 256, 0, ctx->stream>>>((const MinmaxGroup*)base, ctx->N,
-                                                                        (double*)(base + o_part));
+        ScratchPlan sp;
+        auto d_groups = sp.take<MinmaxGroup>(ng);
+        auto d_part = sp.tail<double>(part_doubles);
+        GD_TRY(sp.get(ctx));
+        GD_TRY(gd_h2d(ctx, d_groups, groups.data(), (size_t)ng * sizeof(MinmaxGroup)));
+        k_minmax_affine_grouped<<<dim3(nblk, ng), 256, 0, ctx->stream>>>(d_groups, ctx->N, d_part);
         GD_KERNEL_CHECK();
         std::vector<double> h((size_t)part_doubles);
-        GD_TRY(gd_fetch(ctx, h.data(), base + o_part, h.size() * 8));
+        GD_TRY(gd_fetch(ctx, h.data(), d_part, h.size() * 8));
         GD_TRY(gd_stream_sync(ctx));
         for (int g = 0; g < ng; ++g)
             for (int p = 0; p < groups[g].npairs; ++p) {
@@ -2168,11 +2138,10 @@ int gd_minmax_affine(gd_ctx* ctx, int32_t B, const int32_t* coli, const int32_t*
     int nblk = (4 * ctx->cu_count + B - 1) / B;
     if (nblk < 8) nblk = 8;
     if (nblk > 1024) nblk = 1024;
-    const int64_t o_part = ((int64_t)B * sizeof(Hist2DPair) + 255) / 256 * 256;
-    char* base = (char*)gd_scratch(ctx, o_part + (int64_t)B * nblk * 16);
-    if (!base) return GD_ERR_NOMEM;
-    Hist2DPair* d_pairs = (Hist2DPair*)base;
-    double* d_part = (double*)(base + o_part);
+    ScratchPlan sp;
+    auto d_pairs = sp.take<Hist2DPair>(B);
+    auto d_part = sp.tail<double>((int64_t)B * nblk * 2);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
     k_minmax_affine<<<dim3(nblk, B), 256, 0, ctx->stream>>>(d_pairs, ctx->N, d_part);
     GD_KERNEL_CHECK();

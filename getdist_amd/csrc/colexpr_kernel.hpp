@@ -196,7 +196,7 @@ static int ex_eval(gd_ctx* ctx, const int32_t* code, int32_t ncode, const double
     GD_REQUIRE(ctx && code, "null argument");
     GD_REQUIRE(ctx->cols && ctx->N > 0, "no samples uploaded");
     GD_REQUIRE(dst >= GD_EX_TO_COLUMN && dst <= GD_EX_TO_HOST_U8, "unknown destination");
-    GD_REQUIRE(lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
+    GD_REQUIRE_ROWS(lo, hi);
     const bool to_host = dst == GD_EX_TO_HOST_F64 || dst == GD_EX_TO_HOST_U8;
     if (to_host) {
         GD_REQUIRE(host_out, "null argument");
@@ -252,15 +252,16 @@ static int ex_eval(gd_ctx* ctx, const int32_t* code, int32_t ncode, const double
     if (nblk > cap) nblk = cap;
 
     // scratch: block partials | staging of a host destination (index 0 = row `base`) | the tables
-    const int64_t part_bytes = (nblk * 4 * 8 + 255) / 256 * 256;
-    const int64_t stage_bytes = ((to_host ? 2 * npairs * (dst == GD_EX_TO_HOST_F64 ? 8 : 1) : 0) + 255) / 256 * 256;
-    int64_t tab_bytes = 0;
+    int64_t tab_doubles = 0;
     for (int k = 0; k < ntab; ++k)
-        for (int part = 0; part < 3; ++part) tab_bytes += gdex::tab_doubles(tables[k], part) * 8;
-    char* scr = (char*)gd_scratch(ctx, part_bytes + stage_bytes + tab_bytes);
-    if (!scr) return GD_ERR_NOMEM;
+        for (int part = 0; part < 3; ++part) tab_doubles += gdex::tab_doubles(tables[k], part);
+    ScratchPlan sp;
+    auto d_part = sp.take<double>(nblk * 4);
+    auto d_stage = sp.take<unsigned char>(to_host ? 2 * npairs * (dst == GD_EX_TO_HOST_F64 ? 8 : 1) : 0);
+    auto d_tabs = sp.tail<double>(tab_doubles);
+    GD_TRY(sp.get(ctx));
     if constexpr (TAB) {
-        double* d_tab = (double*)(scr + part_bytes + stage_bytes);
+        double* d_tab = d_tabs;
         for (int k = 0; k < ntab; ++k) {
             A.tab[k] = tables[k];
             const double* src[3] = {tables[k].p0, tables[k].p1, tables[k].p2};
@@ -274,7 +275,7 @@ static int ex_eval(gd_ctx* ctx, const int32_t* code, int32_t ncode, const double
             A.tab[k].p0 = at[0], A.tab[k].p1 = at[1], A.tab[k].p2 = at[2];
         }
     }
-    A.part = stats_out ? (double*)scr : nullptr;
+    A.part = stats_out ? d_part.ptr() : nullptr;
     if (dst == GD_EX_TO_COLUMN) {
         A.out_f64 = ctx->cols + (ctx->n + dst_arg) * ctx->ld;
     } else if (dst == GD_EX_TO_AUXW) {
@@ -285,9 +286,9 @@ static int ex_eval(gd_ctx* ctx, const int32_t* code, int32_t ncode, const double
         A.out_f64 = ctx->like_w;
         A.wmul = sw;
     } else if (dst == GD_EX_TO_HOST_F64) {
-        A.out_f64 = (double*)(scr + part_bytes);
+        A.out_f64 = (double*)d_stage.ptr();
     } else {
-        A.out_u8 = (unsigned char*)(scr + part_bytes);
+        A.out_u8 = d_stage;
     }
     k_expr_eval<TAB><<<dim3((unsigned)nblk), EX_THREADS, lds, ctx->stream>>>(A);
     GD_KERNEL_CHECK();

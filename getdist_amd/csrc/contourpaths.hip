@@ -409,66 +409,60 @@ int gd_contour_paths(gd_ctx* ctx, int32_t B, const void* d_grids, const int64_t*
     std::stable_sort(order.begin(), order.end(),
                      [&](int a, int b) { return cp_words(ny[a / nc], nx[a / nc]) > cp_words(ny[b / nc], nx[b / nc]); });
 
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_task = take((int64_t)T * sizeof(CpTask)), o_order = take((int64_t)T * 4), o_x = take(x_count * 8), o_y = take(y_count * 8);
-    const int64_t meta_bytes = off;
-    const int64_t o_cnt = take((T + 1) * 8), o_big = take((T + 1) * 8), o_nl = take((T + 1) * 8), o_st = take((int64_t)B * 4);
-    const int64_t o_bits = take(words * 8), o_pre = take(words * 4);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
+    ScratchPlan sp;
+    auto d_tasks = sp.take<CpTask>(T);
+    auto d_order = sp.take<int>(T);
+    auto d_x = sp.take<double>(x_count);
+    auto d_y = sp.take<double>(y_count);
+    const int64_t meta_bytes = sp.bytes();
+    auto d_cnt = sp.take<long long>(T + 1), d_big = sp.take<long long>(T + 1), d_nl = sp.take<long long>(T + 1);
+    auto d_st = sp.take<int>(B);
+    auto d_bits = sp.take<cp_u64>(words);
+    auto d_pre = sp.take<int>(words);
+    GD_TRY(sp.get(ctx));
 
     std::vector<char> meta((size_t)meta_bytes, 0);
-    CpTask* tasks = (CpTask*)(meta.data() + o_task);
-    memcpy(meta.data() + o_order, order.data(), (size_t)T * 4);
-    memcpy(meta.data() + o_x, x_axes, (size_t)x_count * 8);
-    memcpy(meta.data() + o_y, y_axes, (size_t)y_count * 8);
+    CpTask* tasks = (CpTask*)(meta.data() + d_tasks.off);
+    memcpy(meta.data() + d_order.off, order.data(), (size_t)T * 4);
+    memcpy(meta.data() + d_x.off, x_axes, (size_t)x_count * 8);
+    memcpy(meta.data() + d_y.off, y_axes, (size_t)y_count * 8);
     int64_t woff = 0;
     for (int b = 0; b < B; ++b) {
         for (int c = 0; c < nc; ++c) {
             CpTask& tk = tasks[b * nc + c];
             tk.P = (const double*)d_grids + grid_off[b];
-            tk.x = (const double*)(base + o_x) + x_off[b];
-            tk.y = (const double*)(base + o_y) + y_off[b];
+            tk.x = d_x + x_off[b];
+            tk.y = d_y + y_off[b];
             tk.level = levels[b * nc + c];
             tk.woff = woff;
             woff += cp_words(ny[b], nx[b]);
             tk.ny = ny[b], tk.nx = nx[b], tk.grid = b, tk.first = c == 0;
         }
     }
-    GD_TRY(gd_h2d(ctx, base, meta.data(), (size_t)meta_bytes));
-    const CpTask* d_tasks = (const CpTask*)(base + o_task);
-    const int* d_order = (const int*)(base + o_order);
-    cp_u64* d_bits = (cp_u64*)(base + o_bits);
-    int* d_pre = (int*)(base + o_pre);
-    long long *d_cnt = (long long*)(base + o_cnt), *d_big = (long long*)(base + o_big), *d_nl = (long long*)(base + o_nl);
-    k_cp_count<<<T, CP_THREADS, 0, ctx->stream>>>(d_tasks, d_order, d_cnt, d_big, (int*)(base + o_st), d_bits, d_pre);
+    GD_TRY(gd_h2d(ctx, d_tasks, meta.data(), (size_t)meta_bytes));
+    k_cp_count<<<T, CP_THREADS, 0, ctx->stream>>>(d_tasks, d_order, d_cnt, d_big, d_st, d_bits, d_pre);
     GD_KERNEL_CHECK();
     long long V = 0, Vbig = 0, L = 0;
     GD_TRY(gd_tile_offsets(ctx, d_cnt, T, &V));
     GD_TRY(gd_tile_offsets(ctx, d_big, T, &Vbig));
-    GD_TRY(gd_fetch(ctx, status_out, base + o_st, (size_t)B * 4));
+    GD_TRY(gd_fetch(ctx, status_out, d_st, (size_t)B * 4));
     GD_TRY(gd_stream_sync(ctx));  // the meta block was pageable: the copy has read it by now
     for (int t = 0; t <= T; ++t) task_vert_off[t] = task_loop_off[t] = 0;
     for (int b = 0; b < B; ++b)
         if (status_out[b]) return GD_OK;  // a non-finite grid: the caller reports it, nothing is traced
     if (V == 0) return GD_OK;
 
-    off = 0;
-    const int64_t o_tab = take(Vbig * CP_SLOT_BYTES), o_xy = take(V * 16), o_ls = take(V * 4), o_loops = take(V * 4),
-                  o_flag = take(V);
-    char* work = (char*)gd_scratch2(ctx, off);
-    if (!work) return GD_ERR_NOMEM;
-    k_cp_paths<<<T, CP_THREADS, 0, ctx->stream>>>(d_tasks, d_order, d_cnt, d_big, d_bits, d_pre, work + o_tab,
-                                                  (double2*)(work + o_xy), (unsigned char*)(work + o_flag), (int*)(work + o_ls),
-                                                  d_nl);
+    ScratchPlan work;
+    auto d_tab = work.take<char>(Vbig * CP_SLOT_BYTES);
+    auto d_xy = work.take<double2>(V);
+    auto d_ls = work.take<int>(V);
+    auto d_loops = work.take<int>(V);
+    auto d_flag = work.take<unsigned char>(V);
+    GD_TRY(work.get2(ctx));
+    k_cp_paths<<<T, CP_THREADS, 0, ctx->stream>>>(d_tasks, d_order, d_cnt, d_big, d_bits, d_pre, d_tab, d_xy, d_flag, d_ls, d_nl);
     GD_KERNEL_CHECK();
     GD_TRY(gd_tile_offsets(ctx, d_nl, T, &L));
-    k_cp_pack_loops<<<T, 256, 0, ctx->stream>>>(d_cnt, d_nl, (const int*)(work + o_ls), (int*)(work + o_loops));
+    k_cp_pack_loops<<<T, 256, 0, ctx->stream>>>(d_cnt, d_nl, d_ls, d_loops);
     GD_KERNEL_CHECK();
     GD_TRY(gd_fetch(ctx, task_vert_off, d_cnt, (size_t)(T + 1) * 8));
     GD_TRY(gd_fetch(ctx, task_loop_off, d_nl, (size_t)(T + 1) * 8));
@@ -477,9 +471,9 @@ int gd_contour_paths(gd_ctx* ctx, int32_t B, const void* d_grids, const int64_t*
     void* h_flag = alloc(user, GD_PATHS_FLAG, V);
     void* h_loops = alloc(user, GD_PATHS_LOOPS, L);
     if (!h_xy || !h_flag || !h_loops) return gd_fail(ctx, GD_ERR_NOMEM, "the caller could not allocate the result arrays");
-    GD_TRY(gd_fetch(ctx, h_xy, work + o_xy, (size_t)V * 16));
-    GD_TRY(gd_fetch(ctx, h_flag, work + o_flag, (size_t)V));
-    GD_TRY(gd_fetch(ctx, h_loops, work + o_loops, (size_t)L * 4));
+    GD_TRY(gd_fetch(ctx, h_xy, d_xy, (size_t)V * 16));
+    GD_TRY(gd_fetch(ctx, h_flag, d_flag, (size_t)V));
+    GD_TRY(gd_fetch(ctx, h_loops, d_loops, (size_t)L * 4));
     GD_TRY(gd_stream_sync(ctx));
     return GD_OK;
 }

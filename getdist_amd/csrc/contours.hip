@@ -154,21 +154,16 @@ int gd_contour_levels(gd_ctx* ctx, int32_t B, int32_t F, const void* d_P, const 
     GD_REQUIRE(ctx && d_P && contours && out && status_out && B > 0, "bad argument");
     GD_REQUIRE(F >= 2 && F <= 4096, "grid size out of range");
     GD_REQUIRE(nc >= 1 && nc <= CL_MAXC, "1..8 contours per call");
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_c = take(nc * 8), o_out = take((int64_t)B * nc * 8), o_st = take((int64_t)B * 4);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    GD_TRY(gd_h2d(ctx, base + o_c, contours, (size_t)nc * 8));
-    k_contour_levels<<<B, 1024, 0, ctx->stream>>>((const double*)d_P, F, (const double*)(base + o_c), nc,
-                                                  (double*)(base + o_out), (int*)(base + o_st));
+    ScratchPlan sp;
+    auto d_c = sp.take<double>(nc);
+    auto d_out = sp.take<double>((int64_t)B * nc);
+    auto d_st = sp.take<int>(B);
+    GD_TRY(sp.get(ctx));
+    GD_TRY(gd_h2d(ctx, d_c, contours, (size_t)nc * 8));
+    k_contour_levels<<<B, 1024, 0, ctx->stream>>>((const double*)d_P, F, d_c, nc, d_out, d_st);
     GD_KERNEL_CHECK();
-    GD_TRY(gd_fetch(ctx, out, base + o_out, (size_t)B * nc * 8));
-    GD_TRY(gd_fetch(ctx, status_out, base + o_st, (size_t)B * 4));
+    GD_TRY(gd_fetch(ctx, out, d_out, (size_t)B * nc * 8));
+    GD_TRY(gd_fetch(ctx, status_out, d_st, (size_t)B * 4));
     GD_TRY(gd_stream_sync(ctx));
     return GD_OK;
 }

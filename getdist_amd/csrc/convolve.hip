@@ -93,12 +93,10 @@ extern "C" {
 int gd_circ_convolve(gd_ctx* ctx, int32_t n0, int32_t n1, const double* a, const double* b, double* out) {
     GD_REQUIRE(ctx && a && b && out && n0 >= 1 && n1 >= 2, "bad argument");
     const int64_t nr = (int64_t)n0 * n1, nc = (int64_t)n0 * (n1 / 2 + 1);
-    auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
-    const int64_t o_a = 0, o_b = up(nr * 8), o_za = o_b + up(nr * 8), o_zb = o_za + up(nc * 16), total = o_zb + up(nc * 16);
-    char* base = (char*)gd_scratch(ctx, total);
-    if (!base) return GD_ERR_NOMEM;
-    double *d_a = (double*)(base + o_a), *d_b = (double*)(base + o_b);
-    double2 *za = (double2*)(base + o_za), *zb = (double2*)(base + o_zb);
+    ScratchPlan sp;
+    auto d_a = sp.take<double>(nr), d_b = sp.take<double>(nr);
+    auto za = sp.take<double2>(nc), zb = sp.take<double2>(nc);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_a, a, (size_t)nr * 8));
     GD_TRY(gd_h2d(ctx, d_b, b, (size_t)nr * 8));
     int rc;
@@ -114,11 +112,10 @@ int gd_circ_convolve(gd_ctx* ctx, int32_t n0, int32_t n1, const double* a, const
 
 int gd_convolve1d_direct(gd_ctx* ctx, const double* x, int64_t nx, const double* y, int64_t ny, double* out_full) {
     GD_REQUIRE(ctx && x && y && out_full && nx >= 1 && ny >= 1, "bad argument");
-    auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
-    const int64_t nout = nx + ny - 1, o_y = up(nx * 8), o_o = o_y + up(ny * 8);
-    char* base = (char*)gd_scratch(ctx, o_o + up(nout * 8));
-    if (!base) return GD_ERR_NOMEM;
-    double *d_x = (double*)base, *d_y = (double*)(base + o_y), *d_o = (double*)(base + o_o);
+    const int64_t nout = nx + ny - 1;
+    ScratchPlan sp;
+    auto d_x = sp.take<double>(nx), d_y = sp.take<double>(ny), d_o = sp.take<double>(nout);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_x, x, (size_t)nx * 8));
     GD_TRY(gd_h2d(ctx, d_y, y, (size_t)ny * 8));
     k_conv1d_direct<<<(unsigned)((nout + 255) / 256 > 4096 ? 4096 : (nout + 255) / 256), 256, 0, ctx->stream>>>(d_x, nx, d_y, ny, d_o);
@@ -137,13 +134,12 @@ int gd_autoconvolve(gd_ctx* ctx, int32_t col, double mean, int32_t use_weights, 
         N = ctx->N;
     }
     GD_REQUIRE(N >= 1 && s >= N && n <= N && s <= 0x7fffffff, "bad sizes");
-    auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
-    const int64_t nc = s / 2 + 1, o_z = up(s * 8), o_o = o_z + up(nc * 16);
-    char* base = (char*)gd_scratch(ctx, o_o + up(n * 8));
-    if (!base) return GD_ERR_NOMEM;
-    double* frame = (double*)base;
-    double2* z = (double2*)(base + o_z);
-    double* d_out = (double*)(base + o_o);
+    const int64_t nc = s / 2 + 1;
+    ScratchPlan sp;
+    auto frame = sp.take<double>(s);
+    auto z = sp.take<double2>(nc);
+    auto d_out = sp.take<double>(n);
+    GD_TRY(sp.get(ctx));
     if (x_host) {
         GD_TRY(gd_h2d(ctx, frame, x_host, (size_t)N * 8));
         GD_HIP(hipMemsetAsync(frame + N, 0, (size_t)(s - N) * 8, ctx->stream));
@@ -169,10 +165,10 @@ int gd_like_stats(gd_ctx* ctx, int32_t col, double* out8) {
     GD_REQUIRE(ctx && out8, "bad argument");
     GD_REQUIRE(ctx->cols && col >= 0 && col < ctx->n + GD_EXTRA_COLS, "column out of range");
     const int nblk = 1024;
-    char* base = (char*)gd_scratch(ctx, (int64_t)nblk * 5 * 8 + 256);
-    if (!base) return GD_ERR_NOMEM;
-    double* d_part = (double*)base;
-    unsigned long long* d_first = (unsigned long long*)(base + (int64_t)nblk * 5 * 8);
+    ScratchPlan plan;  // (`sp` is a sum below)
+    auto d_part = plan.take<double>((int64_t)nblk * 5);
+    auto d_first = plan.take<unsigned long long>(1);
+    GD_TRY(plan.get(ctx));
     const double* L = ctx->cols + (int64_t)col * ctx->ld;
     k_like_pass1<<<nblk, 256, 0, ctx->stream>>>(L, ctx->w, ctx->N, d_part);
     GD_KERNEL_CHECK();

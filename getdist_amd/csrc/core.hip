@@ -786,11 +786,10 @@ int gd_like_weights(gd_ctx* ctx, const double* loglikes, int32_t mode, double me
         GD_HIP(hipMemsetAsync(ctx->like_w, 0, (size_t)(ctx->ld * 8), ctx->stream));
     }
     const int nblk = 2048;
-    const int64_t stage_bytes = (ctx->N * 8 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch(ctx, stage_bytes + nblk * 8);
-    if (!base) return GD_ERR_NOMEM;
-    double* stage = (double*)base;
-    double* d_part = (double*)(base + stage_bytes);
+    ScratchPlan sp;
+    auto stage = sp.take<double>(ctx->N);
+    auto d_part = sp.tail<double>(nblk);
+    GD_TRY(sp.get(ctx));
     GD_HIP(hipMemcpyAsync(stage, loglikes, (size_t)(ctx->N * 8), hipMemcpyHostToDevice, ctx->stream));
     k_like_weights<<<nblk, 256, 0, ctx->stream>>>(ctx->w, stage, ctx->N, mode, mean_loglike, ctx->like_w, d_part);
     GD_KERNEL_CHECK();

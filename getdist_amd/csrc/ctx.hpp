@@ -11,9 +11,11 @@
 #include <set>
 #include <string>
 #include <atomic>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gdhip.h"
+#include "scratchplan.hpp"
 
 struct FftPlanCache;  // density2d.hip
 
@@ -175,6 +177,25 @@ void* gd_scratch2(gd_ctx* ctx, int64_t bytes);
     do {                                                        \
         if (!(cond)) return gd_fail(ctx, GD_ERR_BADARG, "%s", msg); \
     } while (0)
+
+// The row range [lo, hi) of the resident sample set, and a list of its columns: the spare columns behind the sample
+// columns count (GD_REQUIRE_COLUMNS) or are refused (GD_REQUIRE_SAMPLE_COLUMNS).
+#define GD_REQUIRE_ROWS(lo, hi) GD_REQUIRE(ctx->cols && (lo) >= 0 && (hi) <= ctx->N && (lo) < (hi), "bad row range")
+#define GD_REQUIRE_COLUMNS_BELOW(cols, count, bound)                                                                  \
+    do {                                                                                                              \
+        for (int64_t i__ = 0; i__ < (int64_t)(count); ++i__) GD_REQUIRE((cols)[i__] >= 0 && (cols)[i__] < (bound), "column index out of range"); \
+    } while (0)
+#define GD_REQUIRE_COLUMNS(cols, count) GD_REQUIRE_COLUMNS_BELOW(cols, count, ctx->n + GD_EXTRA_COLS)
+#define GD_REQUIRE_SAMPLE_COLUMNS(cols, count) GD_REQUIRE_COLUMNS_BELOW(cols, count, ctx->n)
+
+// Calls f(std::true_type) or f(std::false_type): `gd_by_flag(ctx->w != nullptr, [&](auto HW) { k<HW.value><<<...>>>(..., ctx->w, ...); })`
+// writes the weighted and the unweighted launch once (an unweighted set's ctx->w is null, which is what its kernels
+// are handed).  Two flags nest; a lambda that can fail returns int and goes through GD_TRY.
+template <class F>
+inline auto gd_by_flag(bool flag, F&& f) {
+    if (flag) return f(std::true_type{});
+    return f(std::false_type{});
+}
 
 // ---- device helpers -------------------------------------------------------------------------------
 #define WAVE 64

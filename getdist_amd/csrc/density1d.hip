@@ -415,11 +415,12 @@ int gd_dct1d(gd_ctx* ctx, int32_t B, int32_t F, const double* hist, double* a_ou
     GD_REQUIRE(ctx && hist && a_out && B > 0, "bad argument");
     GD_REQUIRE(F >= 2 && F <= 4096, "fine_bins out of range (2..4096)");
     const int64_t nb = (int64_t)B * F * 8;
-    char* base = (char*)gd_scratch(ctx, 2 * nb + (int64_t)4 * F * 8 + 512);
-    if (!base) return GD_ERR_NOMEM;
-    double* d_in = (double*)base;
-    double* d_out = (double*)(base + (nb + 255) / 256 * 256);
-    double* d_tab = (double*)(base + 2 * ((nb + 255) / 256 * 256));
+    ScratchPlan sp;
+    auto d_in = sp.take<double>((int64_t)B * F);
+    auto d_out = sp.take<double>((int64_t)B * F);
+    auto d_tab = sp.tail<double>((int64_t)4 * F);
+    sp.pad(2 * nb + (int64_t)4 * F * 8 + 512 - sp.bytes());  // the block's size of old: 512 bytes stood for the two roundings
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_in, hist, (size_t)nb));
     k_cos_table<<<(4 * F + 255) / 256, 256, 0, ctx->stream>>>(F, d_tab);
     GD_KERNEL_CHECK();
@@ -435,15 +436,16 @@ static int isj1d_core(gd_ctx* ctx, int32_t B, int32_t F, const double* hist, boo
                       double* hfrac_out, int32_t* status_out) {
     GD_REQUIRE(ctx && hist && neff && hfrac_out && status_out && B > 0, "bad argument");
     GD_REQUIRE(F >= 8 && F <= 4096, "fine_bins out of range (8..4096)");
-    const int64_t nb = ((int64_t)B * F * 8 + 255) / 256 * 256, ns = ((int64_t)B * 16 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch(ctx, 2 * nb + 3 * ns + (int64_t)4 * F * 8 + 512);
-    if (!base) return GD_ERR_NOMEM;
-    const double* d_in = hist_on_device ? hist : (const double*)base;
-    double* d_a = (double*)(base + nb);
-    double* d_neff = (double*)(base + 2 * nb);
-    double* d_nscale = (double*)(base + 2 * nb + ns);
-    double* d_out = (double*)(base + 2 * nb + 2 * ns);
-    double* d_tab = (double*)(base + 2 * nb + 3 * ns);
+    ScratchPlan sp;
+    auto b_in = sp.take<double>((int64_t)B * F);
+    auto d_a = sp.take<double>((int64_t)B * F);
+    auto d_neff = sp.take<double>((int64_t)2 * B);  // (B values in a slot of the result's size)
+    auto d_nscale = sp.take<double>((int64_t)2 * B);
+    auto d_out = sp.take<double>((int64_t)2 * B);
+    auto d_tab = sp.tail<double>((int64_t)4 * F);
+    sp.pad(512);
+    GD_TRY(sp.get(ctx));
+    const double* d_in = hist_on_device ? hist : b_in.ptr();
     // host-side constants with the reference's expressions (kde_bandwidth.py:47-56,63,69,73) in libm arithmetic
     IsjConsts C;
     const double pi = 3.141592653589793;
@@ -460,7 +462,7 @@ static int isj1d_core(gd_ctx* ctx, int32_t B, int32_t F, const double* hist, boo
         GD_REQUIRE(neff[b] > 0, "effective sample number must be positive");
         nscale[b] = pow(neff[b], -1.0 / 5);
     }
-    if (!hist_on_device) GD_TRY(gd_h2d(ctx, (double*)base, hist, (size_t)B * F * 8));
+    if (!hist_on_device) GD_TRY(gd_h2d(ctx, b_in, hist, (size_t)B * F * 8));
     GD_TRY(gd_h2d(ctx, d_neff, neff, (size_t)B * 8));
     GD_TRY(gd_h2d(ctx, d_nscale, nscale.data(), (size_t)B * 8));
     k_cos_table<<<(4 * F + 255) / 256, 256, 0, ctx->stream>>>(F, d_tab);
@@ -492,16 +494,16 @@ static int density1d_core(gd_ctx* ctx, int32_t B, int32_t F, const double* hist,
         GD_REQUIRE(winw[b] >= 0 && 2 * winw[b] + 1 <= F, "window wider than the grid");
         GD_REQUIRE(smooth[b] > 0, "smoothing scale must be positive");
     }
-    const int64_t nb = ((int64_t)B * F * 8 + 255) / 256 * 256, ns = ((int64_t)B * 8 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch(ctx, 2 * nb + 4 * ns);
-    if (!base) return GD_ERR_NOMEM;
-    const double* d_hist = hist_on_device ? hist : (const double*)base;
-    double* d_P = (double*)(base + nb);
-    double* d_smooth = (double*)(base + 2 * nb);
-    int* d_winw = (int*)(base + 2 * nb + ns);
-    int* d_flags = (int*)(base + 2 * nb + 2 * ns);
-    int* d_status = (int*)(base + 2 * nb + 3 * ns);
-    if (!hist_on_device) GD_TRY(gd_h2d(ctx, (double*)base, hist, (size_t)B * F * 8));
+    ScratchPlan sp;
+    auto b_hist = sp.take<double>((int64_t)B * F);
+    auto d_P = sp.take<double>((int64_t)B * F);
+    auto d_smooth = sp.take<double>(B);
+    auto d_winw = sp.take<int>((int64_t)2 * B);  // (B values each; the three int tables keep 8 bytes per curve)
+    auto d_flags = sp.take<int>((int64_t)2 * B);
+    auto d_status = sp.take<int>((int64_t)2 * B);
+    GD_TRY(sp.get(ctx));
+    const double* d_hist = hist_on_device ? hist : b_hist.ptr();
+    if (!hist_on_device) GD_TRY(gd_h2d(ctx, b_hist, hist, (size_t)B * F * 8));
     GD_TRY(gd_h2d(ctx, d_smooth, smooth, (size_t)B * 8));
     GD_TRY(gd_h2d(ctx, d_winw, winw, (size_t)B * 4));
     GD_TRY(gd_h2d(ctx, d_flags, flags, (size_t)B * 4));
@@ -542,13 +544,16 @@ int gd_likes1d(gd_ctx* ctx, int32_t B, int32_t F, const double* hist, const doub
         GD_REQUIRE(winw[b] >= 0 && 2 * winw[b] + 1 <= F, "window wider than the grid");
         GD_REQUIRE(smooth[b] > 0, "smoothing scale must be positive");
     }
-    const int64_t nb = ((int64_t)B * F * 8 + 255) / 256 * 256, ns = ((int64_t)B * 8 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch(ctx, 4 * nb + 4 * ns);
-    if (!base) return GD_ERR_NOMEM;
-    double *d_hist = (double*)base, *d_lh = (double*)(base + nb), *d_P = (double*)(base + 2 * nb),
-           *d_out = (double*)(base + 3 * nb), *d_smooth = (double*)(base + 4 * nb);
-    int *d_winw = (int*)(base + 4 * nb + ns), *d_flags = (int*)(base + 4 * nb + 2 * ns),
-        *d_status = (int*)(base + 4 * nb + 3 * ns);
+    ScratchPlan sp;
+    auto d_hist = sp.take<double>((int64_t)B * F);
+    auto d_lh = sp.take<double>((int64_t)B * F);
+    auto d_P = sp.take<double>((int64_t)B * F);
+    auto d_out = sp.take<double>((int64_t)B * F);
+    auto d_smooth = sp.take<double>(B);
+    auto d_winw = sp.take<int>((int64_t)2 * B);  // (B values each; the three int tables keep 8 bytes per curve)
+    auto d_flags = sp.take<int>((int64_t)2 * B);
+    auto d_status = sp.take<int>((int64_t)2 * B);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_hist, hist, (size_t)B * F * 8));
     GD_TRY(gd_h2d(ctx, d_lh, likehist, (size_t)B * F * 8));
     GD_TRY(gd_h2d(ctx, d_P, P, (size_t)B * F * 8));

@@ -1414,29 +1414,24 @@ static int density2d_periodic(gd_ctx* ctx, int B, int F, const double* d_hist, c
     const int S = next_fft_size(F + 2 * maxw), Sh = S / 2 + 1, Nxh = Nx / 2 + 1;
     const int64_t FF = (int64_t)F * F, SS = (int64_t)S * S, SC = (int64_t)S * Sh, NN = (int64_t)Ny * Nx,
                   NC = (int64_t)Ny * Nxh;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
     const bool need_S = (do_bc || do_mbc) && !ov;
-    const int64_t o_kwin = take(ov ? (int64_t)(2 * maxw + 1) * (2 * maxw + 1) * 8 : 0);
-    const int64_t o_pairs = take((int64_t)B * sizeof(D2Pair)), o_wsum = take((int64_t)B * 8), o_mx = take((int64_t)B * 8 * PM_PARTS),
-                  o_status = take((int64_t)B * 4), o_RC = take(B * NN * 8), o_ROc = take(B * NN * 8),
-                  o_ZHc = take(B * NC * 16), o_ZWc = take(B * NC * 16), o_ZKc = take(B * NC * 16),
-                  o_ZPc = take(B * NC * 16), o_RF = take(need_S ? B * SS * 8 : 0), o_RO = take(need_S ? B * SS * 8 : 0),
-                  o_ZW = take(need_S ? B * SC * 16 : 0), o_ZM = take(need_S ? B * SC * 16 : 0),
-                  o_ZK = take(need_S ? B * SC * 16 : 0), o_ZP = take(need_S ? B * SC * 16 : 0),
-                  o_arr = take((do_bc ? (bco == 1 ? 8 : 1) : 0) * B * FF * 8), o_a00m = take(do_mbc ? B * FF * 8 : 0),
-                  o_conv = take(B * FF * 8), o_box = take(do_mbc ? B * FF * 8 : 0);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    D2Pair* d_pairs = (D2Pair*)(base + o_pairs);
-    double* d_wsum = (double*)(base + o_wsum);
-    double* d_mx = (double*)(base + o_mx);
-    int* d_status = (int*)(base + o_status);
-    double* d_kwin = (double*)(base + o_kwin);
+    ScratchPlan sp;
+    auto d_kwin = sp.take<double>(ov ? (int64_t)(2 * maxw + 1) * (2 * maxw + 1) : 0);
+    auto d_pairs = sp.take<D2Pair>(B);
+    auto d_wsum = sp.take<double>(B);
+    auto d_mx = sp.take<double>((int64_t)B * PM_PARTS);
+    auto d_status = sp.take<int>(B);
+    auto b_RC = sp.take<double>(B * NN), b_ROc = sp.take<double>(B * NN);
+    auto b_ZHc = sp.take<double2>(B * NC), b_ZWc = sp.take<double2>(B * NC), b_ZKc = sp.take<double2>(B * NC),
+         b_ZPc = sp.take<double2>(B * NC);
+    auto b_RF = sp.take<double>(need_S ? B * SS : 0), b_RO = sp.take<double>(need_S ? B * SS : 0);
+    auto b_ZW = sp.take<double2>(need_S ? B * SC : 0), b_ZM = sp.take<double2>(need_S ? B * SC : 0),
+         b_ZK = sp.take<double2>(need_S ? B * SC : 0), b_ZP = sp.take<double2>(need_S ? B * SC : 0);
+    auto b_arr = sp.take<double>((do_bc ? (bco == 1 ? 8 : 1) : 0) * B * FF);
+    auto b_a00m = sp.take<double>(do_mbc ? B * FF : 0);
+    auto b_conv = sp.take<double>(B * FF);
+    auto b_box = sp.take<double>(do_mbc ? B * FF : 0);
+    GD_TRY(sp.get(ctx));
     // a mask moment of the explicit mask: dst = conv(mask, Win x^px y^py, 'valid')
     auto direct_moment = [&](const double* mask, int px_, int py_, double* dst) -> int {
         if (!mask) return gd_fail(ctx, GD_ERR_BADARG, "explicit mask missing for a requested correction");
@@ -1446,12 +1441,8 @@ static int density2d_periodic(gd_ctx* ctx, int B, int F, const double* d_hist, c
         if (hipGetLastError() != hipSuccess) return gd_fail(ctx, GD_ERR_HIP, "k_mask_moment_direct launch failed");
         return GD_OK;
     };
-    double *RC = (double*)(base + o_RC), *ROc = (double*)(base + o_ROc), *RF = (double*)(base + o_RF),
-           *RO = (double*)(base + o_RO), *arr = (double*)(base + o_arr), *d_a00m = (double*)(base + o_a00m),
-           *d_conv = (double*)(base + o_conv), *d_box = (double*)(base + o_box);
-    double2 *ZHc = (double2*)(base + o_ZHc), *ZWc = (double2*)(base + o_ZWc), *ZKc = (double2*)(base + o_ZKc),
-            *ZPc = (double2*)(base + o_ZPc), *ZW = (double2*)(base + o_ZW), *ZM = (double2*)(base + o_ZM),
-            *ZK = (double2*)(base + o_ZK), *ZP = (double2*)(base + o_ZP);
+    double *RC = b_RC, *ROc = b_ROc, *RF = b_RF, *RO = b_RO, *arr = b_arr, *d_a00m = b_a00m, *d_conv = b_conv, *d_box = b_box;
+    double2 *ZHc = b_ZHc, *ZWc = b_ZWc, *ZKc = b_ZKc, *ZPc = b_ZPc, *ZW = b_ZW, *ZM = b_ZM, *ZK = b_ZK, *ZP = b_ZP;
     if (wait) {
         GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(D2Pair)));
     } else {  // hp dies with this frame before the copy executes
@@ -1630,12 +1621,6 @@ static int density2d_main(gd_ctx* ctx, int32_t B, int32_t F, const void* d_hist_
     // prior-mask moments come from summed-area tables of the window (k_window_sat / k_mask_eval)
     const int n_mom = (do_bc ? (bco == 1 ? 6 : 1) : 0) + (mbc ? 1 : 0);
     const int64_t sat_stride = (int64_t)(2 * maxw + 2) * (2 * maxw + 2);
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
     // ---- route: transforms in LDS (three kernels per convolution) where the frame, the window table and the grid fit
     FftDev pl, plH;  // plans of the frame length (columns) and of half of it (the real rows, packed)
     const double2* d_tw = nullptr;
@@ -1671,37 +1656,29 @@ static int density2d_main(gd_ctx* ctx, int32_t B, int32_t F, const void* d_hist_
     const int64_t tab_stride = (int64_t)(2 * maxw + 3) * (2 * maxw + 3);
     const int64_t XT = (int64_t)B * ((F + 15) / 16) * 16 * Sh * 16;  // tiled half spectra of the LDS route (whole tiles of 16 rows)
     const int64_t WT = (int64_t)B * Sh * S * 8;  // a window moment's spectrum by columns (its real or its imaginary part)
-    const int64_t o_pairs = take((int64_t)B * sizeof(D2Pair)), o_wsum = take((int64_t)B * 8), o_mx = take((int64_t)B * 8 * PM_PARTS),
-                  o_mx2 = take((int64_t)B * 8 * PM_PARTS),
-                  o_status = take((int64_t)B * 4), o_RF = take(lds_conv ? XT : B * SS * 8), o_RO = take(lds_conv ? XT : B * SS * 8),
-                  o_ZH = take(lds_conv ? WT : B * SC * 16), o_ZW = take(lds_conv ? WT : B * SC * 16),
-                  o_ZK = take(!lds_conv && do_bc && bco == 1 ? B * SC * 16 : 0), o_ZP = take(lds_conv ? 0 : B * SC * 16),
-                  o_arr = take((do_bc ? (bco == 1 ? (fused ? 2 : 8) : (fused ? 0 : 1)) : 0) * B * FF * 8),
-                  o_a00m = take(mbc && !fused ? B * FF * 8 : 0),
-                  o_conv = take(mbc ? B * FF * 8 : 0), o_sat = take((int64_t)n_mom * B * sat_stride * 8),
-                  o_tab = take(class_tables ? (int64_t)n_mom * B * tab_stride * 8 : 0),
-                  o_wtab = take(lds_conv && wglob ? (int64_t)B * Mmax * Mmax * 8 : 0),
-                  o_rowdft = take(lds_conv && wglob ? (int64_t)B * Mmax * Sh * 16 : 0);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    D2Pair* d_pairs = (D2Pair*)(base + o_pairs);
-    double* d_wsum = (double*)(base + o_wsum);
-    double* d_mx = (double*)(base + o_mx);    // block maxima of the current grid ...
-    double* d_mx2 = (double*)(base + o_mx2);  // ... and the set the boundary correction writes while it reads the other
-    int* d_status = (int*)(base + o_status);
-    double* RF = (double*)(base + o_RF);
-    double* RO = (double*)(base + o_RO);
-    double2* ZH = (double2*)(base + o_ZH);
-    double2* ZW = (double2*)(base + o_ZW);
-    double2* ZK = (double2*)(base + o_ZK);
-    double2* ZP = (double2*)(base + o_ZP);
-    double* arr = (double*)(base + o_arr);
-    double* d_a00m = (double*)(base + o_a00m);
-    double* d_conv = (double*)(base + o_conv);
-    double* d_sat = (double*)(base + o_sat);
-    double* d_tab = class_tables ? (double*)(base + o_tab) : nullptr;
-    double* d_wtab = (double*)(base + o_wtab);
-    double2* d_rowdft = (double2*)(base + o_rowdft);
+    ScratchPlan sp;
+    auto d_pairs = sp.take<D2Pair>(B);
+    auto d_wsum = sp.take<double>(B);
+    auto d_mx = sp.take<double>((int64_t)B * PM_PARTS);   // block maxima of the current grid ...
+    auto d_mx2 = sp.take<double>((int64_t)B * PM_PARTS);  // ... and the set the boundary correction writes while it reads the other
+    auto d_status = sp.take<int>(B);
+    auto b_RF = sp.take<double>(lds_conv ? XT / 8 : B * SS);
+    auto b_RO = sp.take<double>(lds_conv ? XT / 8 : B * SS);
+    auto b_ZH = sp.take<double2>(lds_conv ? WT / 16 : B * SC);
+    auto b_ZW = sp.take<double2>(lds_conv ? WT / 16 : B * SC);
+    auto b_ZK = sp.take<double2>(!lds_conv && do_bc && bco == 1 ? B * SC : 0);
+    auto b_ZP = sp.take<double2>(lds_conv ? 0 : B * SC);
+    auto b_arr = sp.take<double>((do_bc ? (bco == 1 ? (fused ? 2 : 8) : (fused ? 0 : 1)) : 0) * B * FF);
+    auto b_a00m = sp.take<double>(mbc && !fused ? B * FF : 0);
+    auto b_conv = sp.take<double>(mbc ? B * FF : 0);
+    auto b_sat = sp.take<double>((int64_t)n_mom * B * sat_stride);
+    auto b_tab = sp.take<double>(class_tables ? (int64_t)n_mom * B * tab_stride : 0);
+    auto b_wtab = sp.take<double>(lds_conv && wglob ? (int64_t)B * Mmax * Mmax : 0);
+    auto b_rowdft = sp.take<double2>(lds_conv && wglob ? (int64_t)B * Mmax * Sh : 0);
+    GD_TRY(sp.get(ctx));
+    double *RF = b_RF, *RO = b_RO, *arr = b_arr, *d_a00m = b_a00m, *d_conv = b_conv, *d_sat = b_sat, *d_wtab = b_wtab;
+    double2 *ZH = b_ZH, *ZW = b_ZW, *ZK = b_ZK, *ZP = b_ZP, *d_rowdft = b_rowdft;
+    double* d_tab = class_tables ? b_tab.ptr() : nullptr;
     if (wait) {
         GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(D2Pair)));
     } else {  // hp dies with this frame before the copy executes
@@ -1976,21 +1953,24 @@ int gd_density2d_masked(gd_ctx* ctx, int32_t F, const void* d_hist, double rx, d
                         const unsigned char* zero_mask, void* d_P_out, int32_t* status_out) {
     GD_REQUIRE(ctx && d_hist && d_P_out && status_out, "bad argument");
     GD_REQUIRE(F >= 8 && F <= 4096 && winw >= 1 && winw <= 2 * F, "bad grid size / window half-width");
-    const int64_t Mp = (int64_t)F + 2 * winw, nb = (Mp * Mp * 8 + 255) / 256 * 256, nz = ((int64_t)F * F + 255) / 256 * 256;
-    char* base = (char*)gd_scratch2(ctx, 2 * nb + nz);
-    if (!base) return GD_ERR_NOMEM;
+    const int64_t Mp = (int64_t)F + 2 * winw;
+    ScratchPlan sp;
+    auto d_bc = sp.take<double>(Mp * Mp);
+    auto d_mbc = sp.take<double>(Mp * Mp);
+    auto d_zero = sp.take<unsigned char>((int64_t)F * F);
+    GD_TRY(sp.get2(ctx));
     MaskOv ov{nullptr, nullptr, nullptr};
     if (mask_bc) {
-        GD_TRY(gd_h2d(ctx, base, mask_bc, (size_t)(Mp * Mp * 8)));
-        ov.d_mask_bc = (const double*)base;
+        GD_TRY(gd_h2d(ctx, d_bc, mask_bc, (size_t)(Mp * Mp * 8)));
+        ov.d_mask_bc = d_bc;
     }
     if (mask_mbc) {
-        GD_TRY(gd_h2d(ctx, base + nb, mask_mbc, (size_t)(Mp * Mp * 8)));
-        ov.d_mask_mbc = (const double*)(base + nb);
+        GD_TRY(gd_h2d(ctx, d_mbc, mask_mbc, (size_t)(Mp * Mp * 8)));
+        ov.d_mask_mbc = d_mbc;
     }
     if (zero_mask) {
-        GD_TRY(gd_h2d(ctx, base + 2 * nb, zero_mask, (size_t)F * F));
-        ov.d_zero = (const unsigned char*)(base + 2 * nb);
+        GD_TRY(gd_h2d(ctx, d_zero, zero_mask, (size_t)F * F));
+        ov.d_zero = d_zero;
     }
     const int32_t fl = flags | 64;  // a mask function always counts as a prior (mcsamples.py:1794)
     return density2d_main(ctx, 1, F, d_hist, &rx, &ry, &corr, &winw, &fl, bco, mbc, d_P_out, status_out, &ov);
@@ -2029,23 +2009,14 @@ int gd_likes2d(gd_ctx* ctx, int32_t B, int32_t F, const void* d_hist_v, const vo
     const int n0 = py ? F - 1 : F, n1 = px ? F - 1 : F;
     if (per) GD_REQUIRE(2 * maxw + 1 <= n1 && 2 * maxw + 1 <= n0, "window wider than the periodic grid");
     const int64_t FF = (int64_t)F * F, NN = (int64_t)n0 * n1;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_pairs = take((int64_t)B * sizeof(D2Pair)), o_wsum = take((int64_t)B * 8), o_mx = take((int64_t)B * 8 * PM_PARTS),
-                  o_status = take((int64_t)B * 4), o_C1 = take(per ? B * NN * 8 : 0), o_C2 = take(per ? B * NN * 8 : 0),
-                  o_P0 = take(B * FF * 8), o_T = take(B * FF * 8), o_L2 = take(B * FF * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    D2Pair* d_pairs = (D2Pair*)(base + o_pairs);
-    double* d_wsum = (double*)(base + o_wsum);
-    double* d_mx = (double*)(base + o_mx);
-    int* d_status = (int*)(base + o_status);
-    double *C1 = (double*)(base + o_C1), *C2 = (double*)(base + o_C2), *d_P0 = (double*)(base + o_P0),
-           *d_T = (double*)(base + o_T), *d_L2 = (double*)(base + o_L2);
+    ScratchPlan sp;
+    auto d_pairs = sp.take<D2Pair>(B);
+    auto d_wsum = sp.take<double>(B);
+    auto d_mx = sp.take<double>((int64_t)B * PM_PARTS);
+    auto d_status = sp.take<int>(B);
+    auto C1 = sp.take<double>(per ? B * NN : 0), C2 = sp.take<double>(per ? B * NN : 0);
+    auto d_P0 = sp.take<double>(B * FF), d_T = sp.take<double>(B * FF), d_L2 = sp.take<double>(B * FF);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(D2Pair)));
     const dim3 gN(64, B), gF(64, B);
     const dim3 gC((unsigned)(((n1 + 63) / 64) * ((n0 + 4 * CONV_RY - 1) / (4 * CONV_RY))), B);

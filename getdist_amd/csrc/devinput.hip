@@ -292,9 +292,10 @@ int device_build(gd_ctx* ctx, const gd_dev_part* parts, int nparts, int dtype, i
     double* cols = *cols_out;
     GD_HIP(hipMemsetAsync(cols + ld * m, 0, (size_t)(ld * GD_EXTRA_COLS * 8), ctx->stream));
     // the kept-column list, in a scratch block large enough for the weight step that follows on the same stream
-    const int64_t keep_bytes = (m * 4 + 255) / 256 * 256;
-    int* d_keep = (int*)gd_scratch(ctx, keep_bytes + (64 << 10));
-    if (!d_keep) return GD_ERR_NOMEM;
+    ScratchPlan sp;
+    auto d_keep = sp.take<int>(m);
+    sp.pad(64 << 10);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_keep, keep.data(), (size_t)m * 4));
     int64_t at = 0;
     for (int k = 0; k < nparts; ++k) {

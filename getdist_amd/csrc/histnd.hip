@@ -286,6 +286,7 @@ int gd_histnd_batch(gd_ctx* ctx, int32_t B, const int32_t* dims, const int32_t* 
     std::vector<int32_t> ucol;
     std::vector<double> ubmin, uwidth;
     std::vector<int> slot((size_t)first[B]);
+    GD_REQUIRE_COLUMNS(cols, first[B]);
     for (int t = 0; t < first[B]; ++t) {
         GD_REQUIRE(cols[t] >= 0 && cols[t] < ctx->n + GD_EXTRA_COLS, "column out of range");
         GD_REQUIRE(width[t] > 0 && std::isfinite(width[t]) && std::isfinite(binmin[t]), "bad bin width / origin");
@@ -299,7 +300,6 @@ int gd_histnd_batch(gd_ctx* ctx, int32_t B, const int32_t* dims, const int32_t* 
     }
     const int nu = (int)ucol.size();
     const bool u8 = nb <= 256;
-    const int64_t col_bytes = ((N + 64) * (u8 ? 1 : 2) + 255) / 256 * 256;  // padded: the kernel reads 4 rows at a time
     // tiers
     const int wm = !ctx->w ? 0 : (ctx->w_integral ? 1 : 2);
     const int hbytes = (flags & GD_HISTND_H) ? (wm == 2 ? 8 : 4) : 0;
@@ -316,20 +316,17 @@ int gd_histnd_batch(gd_ctx* ctx, int32_t B, const int32_t* dims, const int32_t* 
         }
     }
     // device scratch: index columns, descriptors, lists, grids (u64 per output), max words, bad counter
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_idx = take((int64_t)nu * col_bytes), o_desc = take((int64_t)B * sizeof(HistNDDesc)),
-                  o_list = take((int64_t)B * 4), o_H = take((flags & GD_HISTND_H) ? total * 8 : 8),
-                  o_HL = take((flags & GD_HISTND_LIKES) ? total * 8 : 8), o_L = take((flags & GD_HISTND_LMIN) ? total * 8 : 8),
-                  o_misc = take(64);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    std::vector<void*> ubuf((size_t)nu);
-    for (int u = 0; u < nu; ++u) ubuf[u] = base + o_idx + (int64_t)u * col_bytes;
+    ScratchPlan sp;
+    std::vector<ScratchPlan::Buf<unsigned char>> d_idx;  // padded by 64 rows: the kernel reads 4 rows at a time
+    for (int u = 0; u < nu; ++u) d_idx.push_back(sp.take<unsigned char>((N + 64) * (u8 ? 1 : 2)));
+    auto d_desc = sp.take<HistNDDesc>(B);
+    auto d_list = sp.take<int>(B);
+    auto gH = sp.take<unsigned long long>((flags & GD_HISTND_H) ? total : 1);
+    auto gHL = sp.take<unsigned long long>((flags & GD_HISTND_LIKES) ? total : 1);
+    auto gL = sp.take<unsigned long long>((flags & GD_HISTND_LMIN) ? total : 1);
+    auto d_wmax = sp.take<unsigned long long>(8);  // two maxima, then the bad-sample counter
+    GD_TRY(sp.get(ctx));
+    std::vector<void*> ubuf(d_idx.begin(), d_idx.end());
     for (int b = 0; b < B; ++b)
         for (int a = 0; a < dims[b]; ++a) hd[b].idx[a] = ubuf[slot[first[b] + a]];
     // index columns (these calls wait for their kernels: the columns are complete when they return)
@@ -342,12 +339,6 @@ int gd_histnd_batch(gd_ctx* ctx, int32_t B, const int32_t* dims, const int32_t* 
     } else {
         GD_TRY(gd_prebin_batch(ctx, ucol.data(), nu, ubmin.data(), uwidth.data(), nb, ubuf.data()));
     }
-    HistNDDesc* d_desc = (HistNDDesc*)(base + o_desc);
-    int* d_list = (int*)(base + o_list);
-    unsigned long long* gH = (unsigned long long*)(base + o_H);
-    unsigned long long* gHL = (unsigned long long*)(base + o_HL);
-    unsigned long long* gL = (unsigned long long*)(base + o_L);
-    unsigned long long* d_wmax = (unsigned long long*)(base + o_misc);
     unsigned long long* d_bad = d_wmax + 2;
     std::vector<int> lists(lds_list);
     lists.insert(lists.end(), glob_list.begin(), glob_list.end());

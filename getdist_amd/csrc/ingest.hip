@@ -433,10 +433,11 @@ static int scan_common(gd_ctx* ctx, ParseArgs& p, ScanOut* o) {
     const int64_t nb64 = (p.phase0 + p.nbytes + ING_TB - 1) / ING_TB;
     GD_REQUIRE(nb64 < (1LL << 30), "too much text for one call");
     o->nb = (int)nb64;
-    char* scr = (char*)gd_scratch(ctx, ((int64_t)o->nb + 1) * 8 + (int64_t)sizeof(ParseRes));
-    if (!scr) return GD_ERR_NOMEM;
-    o->cnt = (long long*)scr;
-    o->d_res = (ParseRes*)(scr + ((int64_t)o->nb + 1) * 8);
+    ScratchPlan sp;
+    auto cnt = sp.tail<long long>((int64_t)o->nb + 1);  // (tail: the result record follows at once)
+    auto d_res = sp.tail<ParseRes>(1);
+    GD_TRY(sp.get(ctx));
+    o->cnt = cnt, o->d_res = d_res;
     k_ingest_init<<<1, 1, 0, ctx->stream>>>(o->d_res, (long long)p.nbytes);
     GD_KERNEL_CHECK();
     ParseArgs q = p;

@@ -1191,29 +1191,24 @@ extern "C" {
 int gd_get_h(gd_ctx* ctx, int32_t B, const double* psi, const double* neff, const double* corr, const int32_t* do_corr,
              double* out) {
     GD_REQUIRE(ctx && psi && neff && corr && do_corr && out && B > 0, "bad argument");
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_k = take((int64_t)B * KOPT_STRIDE * 8), o_n = take((int64_t)B * 8), o_c = take((int64_t)B * 8),
-                  o_d = take((int64_t)B * 4);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
+    ScratchPlan sp;
+    auto d_k = sp.take<double>((int64_t)B * KOPT_STRIDE);
+    auto d_n = sp.take<double>(B);
+    auto d_c = sp.take<double>(B);
+    auto d_d = sp.take<int>(B);
+    GD_TRY(sp.get(ctx));
     std::vector<double> hk((size_t)B * KOPT_STRIDE, 0.0);
     for (int b = 0; b < B; ++b) {
         for (int q = 0; q < 6; ++q) hk[(size_t)b * KOPT_STRIDE + 1 + q] = psi[(size_t)b * 6 + q];
         hk[(size_t)b * KOPT_STRIDE + 7] = (double)GD_OK;
     }
-    GD_TRY(gd_h2d(ctx, base + o_k, hk.data(), hk.size() * 8));
-    GD_TRY(gd_h2d(ctx, base + o_n, neff, (size_t)B * 8));
-    GD_TRY(gd_h2d(ctx, base + o_c, corr, (size_t)B * 8));
-    GD_TRY(gd_h2d(ctx, base + o_d, do_corr, (size_t)B * 4));
-    k_get_h<<<B, 64, 0, ctx->stream>>>((double*)(base + o_k), (const double*)(base + o_n), (const double*)(base + o_c),
-                                      (const int*)(base + o_d), B);
+    GD_TRY(gd_h2d(ctx, d_k, hk.data(), hk.size() * 8));
+    GD_TRY(gd_h2d(ctx, d_n, neff, (size_t)B * 8));
+    GD_TRY(gd_h2d(ctx, d_c, corr, (size_t)B * 8));
+    GD_TRY(gd_h2d(ctx, d_d, do_corr, (size_t)B * 4));
+    k_get_h<<<B, 64, 0, ctx->stream>>>(d_k, d_n, d_c, d_d, B);
     GD_KERNEL_CHECK();
-    GD_TRY(gd_fetch(ctx, hk.data(), base + o_k, hk.size() * 8));
+    GD_TRY(gd_fetch(ctx, hk.data(), d_k, hk.size() * 8));
     GD_TRY(gd_stream_sync(ctx));
     for (int b = 0; b < B; ++b)
         for (int q = 0; q < 4; ++q) out[(size_t)b * 4 + q] = hk[(size_t)b * KOPT_STRIDE + 8 + q];
@@ -1282,33 +1277,24 @@ static int kopt_stage_a(gd_ctx* ctx, int32_t B, int32_t F, const void* d_hist_v,
     }
     const int nc = (int)which.size();
     const int Fh = F / 2 + 1;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
     // the per-pair tables sit next to one another: ONE staged upload instead of five pageable copies (each of which
     // would wait for the copy engine behind the previous call's result copies)
-    const int64_t o_pairs = take((int64_t)B * sizeof(KoptPair)), o_which = take((int64_t)(nc + 1) * 4);
-    const int64_t table_bytes = off;
-    const int64_t o_sums = take((int64_t)B * 8), o_E = take((int64_t)B * FF * 8),
-                  o_SQ = take((int64_t)B * FF * 8), o_Z = take((int64_t)nc * F * Fh * 16), o_PW = take((int64_t)nc * FF * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    double* d_sums = (double*)(base + o_sums);
-    KoptPair* d_pairs = (KoptPair*)(base + o_pairs);
+    ScratchPlan sp;
+    auto d_pairs = sp.take<KoptPair>(B);
+    auto d_which = sp.take<int>(nc + 1);
+    const int64_t table_bytes = sp.bytes();
+    auto d_sums = sp.take<double>(B);
+    auto d_E = sp.take<double>((int64_t)B * FF);
+    auto d_SQ = sp.take<double>((int64_t)B * FF);
+    auto d_Z = sp.take<double2>((int64_t)nc * F * Fh);
+    auto d_PW = sp.take<double>((int64_t)nc * FF);
+    GD_TRY(sp.get(ctx));
     double* d_out = d_rows;
-    int* d_which = (int*)(base + o_which);
-    double* d_E = (double*)(base + o_E);
-    double* d_SQ = (double*)(base + o_SQ);
-    double2* d_Z = (double2*)(base + o_Z);
-    double* d_PW = (double*)(base + o_PW);
     {
         std::vector<char> tab((size_t)table_bytes, 0);
-        memcpy(tab.data() + o_pairs, hp.data(), (size_t)B * sizeof(KoptPair));
-        if (nc) memcpy(tab.data() + o_which, which.data(), (size_t)nc * 4);
-        GD_TRY(gd_stage_h2d(ctx, base, tab.data(), (size_t)table_bytes));
+        memcpy(tab.data() + d_pairs.off, hp.data(), (size_t)B * sizeof(KoptPair));
+        if (nc) memcpy(tab.data() + d_which.off, which.data(), (size_t)nc * 4);
+        GD_TRY(gd_stage_h2d(ctx, d_pairs, tab.data(), (size_t)table_bytes));
     }
     k_hist_sums<<<B, 1024, 0, ctx->stream>>>(d_hist, (int)FF, d_sums);
     GD_KERNEL_CHECK();

@@ -238,27 +238,24 @@ int gd_limits1d(gd_ctx* ctx, int32_t B, int32_t F, const double* P, const double
     if (factor <= 0) factor = 20000 / F > 2 ? 20000 / F : 2;  // densities.py:191-194
     GD_REQUIRE((int64_t)(F - 1) * factor + 1 <= (1 << 22), "refinement factor too large");
     LimArgs A{F, factor, nc, (F - 1) * factor + 1};
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_P = take((int64_t)B * F * 8), o_x = take((int64_t)B * 8), o_s = take((int64_t)B * 8), o_c = take(nc * 8),
-                  o_G = take((int64_t)B * A.bign * 8), o_out = take((int64_t)B * nc * 32), o_st = take((int64_t)B * 4);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    GD_TRY(gd_h2d(ctx, base + o_P, P, (size_t)B * F * 8));
-    GD_TRY(gd_h2d(ctx, base + o_x, x0, (size_t)B * 8));
-    GD_TRY(gd_h2d(ctx, base + o_s, spacing, (size_t)B * 8));
-    GD_TRY(gd_h2d(ctx, base + o_c, contours, (size_t)nc * 8));
+    ScratchPlan sp;
+    auto d_P = sp.take<double>((int64_t)B * F);
+    auto d_x = sp.take<double>(B);
+    auto d_s = sp.take<double>(B);
+    auto d_c = sp.take<double>(nc);
+    auto d_G = sp.take<double>((int64_t)B * A.bign);
+    auto d_out = sp.take<double>((int64_t)B * nc * 4);
+    auto d_st = sp.take<int>(B);
+    GD_TRY(sp.get(ctx));
+    GD_TRY(gd_h2d(ctx, d_P, P, (size_t)B * F * 8));
+    GD_TRY(gd_h2d(ctx, d_x, x0, (size_t)B * 8));
+    GD_TRY(gd_h2d(ctx, d_s, spacing, (size_t)B * 8));
+    GD_TRY(gd_h2d(ctx, d_c, contours, (size_t)nc * 8));
     GD_HIP(hipFuncSetAttribute((const void*)k_limits1d, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 4096 * 8));
-    k_limits1d<<<B, LM_T, (size_t)3 * F * 8, ctx->stream>>>((const double*)(base + o_P), (const double*)(base + o_x),
-                                                           (const double*)(base + o_s), (const double*)(base + o_c), A,
-                                                           (double*)(base + o_G), (double*)(base + o_out), (int*)(base + o_st));
+    k_limits1d<<<B, LM_T, (size_t)3 * F * 8, ctx->stream>>>(d_P, d_x, d_s, d_c, A, d_G, d_out, d_st);
     GD_KERNEL_CHECK();
-    GD_TRY(gd_fetch(ctx, out, base + o_out, (size_t)B * nc * 32));
-    GD_TRY(gd_fetch(ctx, status_out, base + o_st, (size_t)B * 4));
+    GD_TRY(gd_fetch(ctx, out, d_out, (size_t)B * nc * 32));
+    GD_TRY(gd_fetch(ctx, status_out, d_st, (size_t)B * 4));
     GD_TRY(gd_stream_sync(ctx));
     return GD_OK;
 }

@@ -245,8 +245,8 @@ int gd_mixture_nll(gd_ctx* ctx, const int32_t* cols, int32_t d, int32_t K, const
     GD_REQUIRE(ctx->cols && ctx->N > 0, "no samples uploaded (empty row range)");
     GD_REQUIRE(d >= 1 && d <= ctx->n, "mixture dimension out of range (1..uploaded columns)");
     GD_REQUIRE(K >= 1 && (int64_t)K * ((d + MIX_B - 1) / MIX_B) < (1 << 30), "number of mixture components out of range");
-    GD_REQUIRE(row_lo >= 0 && row_hi <= ctx->N && row_lo < row_hi, "bad row range");
-    for (int i = 0; i < d; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n, "mixture column index out of range");
+    GD_REQUIRE_ROWS(row_lo, row_hi);
+    GD_REQUIRE_SAMPLE_COLUMNS(cols, d);
     MixPlan P;
     GD_REQUIRE(mix_plan(d, K, P), "mixture dimension too large for one tile of rows in LDS");
     const int nI = (d + MIX_B - 1) / MIX_B, dp = nI * MIX_B;
@@ -255,42 +255,38 @@ int gd_mixture_nll(gd_ctx* ctx, const int32_t* cols, int32_t d, int32_t K, const
     mix_units(d, K, P.S, table, ucap);
 
     // one host block: W (padded) | mu (padded) | logcoef | colidx | units
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_W = take((int64_t)K * dp * dp * 8), o_mu = take((int64_t)K * dp * 8), o_lc = take((int64_t)K * 8),
-                  o_ci = take((int64_t)d * 4), o_u = take((int64_t)table.size() * 4);
-    const int64_t tab_bytes = off;
+    ScratchPlan sp;
+    auto d_W = sp.take<double>((int64_t)K * dp * dp);
+    auto d_mu = sp.take<double>((int64_t)K * dp);
+    auto d_lc = sp.take<double>(K);
+    auto d_ci = sp.take<int>(d);
+    auto d_u = sp.take<int>((int64_t)table.size());
+    const int64_t tab_bytes = sp.bytes();
     const int64_t n = row_hi - row_lo;
-    const int64_t o_out = take(n * 8);
+    auto d_out = sp.take<double>(n);
     std::vector<char> host((size_t)tab_bytes, 0);
-    double* hW = (double*)(host.data() + o_W);
-    double* hmu = (double*)(host.data() + o_mu);
+    double* hW = (double*)(host.data() + d_W.off);
+    double* hmu = (double*)(host.data() + d_mu.off);
     for (int k = 0; k < K; ++k) {
         for (int i = 0; i < d; ++i) {
             for (int j = 0; j <= i; ++j) hW[((int64_t)k * dp + i) * dp + j] = whiten[((int64_t)k * d + i) * d + j];
             hmu[(int64_t)k * dp + i] = means[(int64_t)k * d + i];
         }
     }
-    memcpy(host.data() + o_lc, logcoef, (size_t)K * 8);
-    memcpy(host.data() + o_ci, cols, (size_t)d * 4);
-    memcpy(host.data() + o_u, table.data(), table.size() * 4);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    GD_TRY(gd_h2d(ctx, base, host.data(), (size_t)tab_bytes));
+    memcpy(host.data() + d_lc.off, logcoef, (size_t)K * 8);
+    memcpy(host.data() + d_ci.off, cols, (size_t)d * 4);
+    memcpy(host.data() + d_u.off, table.data(), table.size() * 4);
+    GD_TRY(sp.get(ctx));
+    GD_TRY(gd_h2d(ctx, d_W, host.data(), (size_t)tab_bytes));
 
     MixArgs A{};
     A.cols = ctx->cols, A.ld = ctx->ld, A.lo = row_lo, A.hi = row_hi;
-    A.colidx = (const int*)(base + o_ci), A.W = (const double*)(base + o_W), A.mu = (const double*)(base + o_mu);
-    A.logcoef = (const double*)(base + o_lc), A.units = (const int*)(base + o_u);
+    A.colidx = d_ci, A.W = d_W, A.mu = d_mu, A.logcoef = d_lc, A.units = d_u;
     A.d = d, A.dp = dp, A.K = K, A.nI = nI, A.G = P.G, A.S = P.S, A.RG = P.RG, A.ucap = ucap;
     const int BR = P.G * P.RG;
     A.brs = 0;
     while ((1 << A.brs) < BR) ++A.brs;
-    A.out = (double*)(base + o_out);
+    A.out = d_out;
     const int64_t nblocks = (n + BR - 1) / BR;
     GD_REQUIRE(nblocks <= 0x7fffffffLL, "row range too long for one launch");
     GD_HIP(hipFuncSetAttribute((const void*)k_mixture_nll, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));

@@ -302,23 +302,16 @@ struct PcaScratch {
 // one scratch block for both passes of a call: tables, group descriptors, S and the partials (max_slots = the larger
 // chunks x groups of the two passes)
 int pca_scratch(gd_ctx* ctx, int nc, int np, int nall, int max_groups, int64_t max_slots, PcaScratch& sc) {
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
     sc.part_cap = max_slots * 16 * 256;
-    const int64_t o_ci = take(nc * 4), o_m = take(nc * 4), o_c = take(8 * (int64_t)(nc + 1)), o_zm = take(8 * (int64_t)nc),
-                  o_zs = take(8 * (int64_t)nc), o_U = take(8 * (int64_t)np * np + 8), o_am = take(8 * (int64_t)nall + 8),
-                  o_as = take(8 * (int64_t)nall + 8), o_g = take((int64_t)max_groups * sizeof(PcaGroup)),
-                  o_S = take((int64_t)max_groups * 16 * 256 * 8), o_p = take(sc.part_cap * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    sc.colidx = (int*)(base + o_ci), sc.maps = (int*)(base + o_m), sc.centre = (double*)(base + o_c);
-    sc.zmean = (double*)(base + o_zm), sc.zsd = (double*)(base + o_zs), sc.U = (double*)(base + o_U);
-    sc.amean = (double*)(base + o_am), sc.asd = (double*)(base + o_as), sc.groups = (PcaGroup*)(base + o_g);
-    sc.S = (double*)(base + o_S), sc.part = (double*)(base + o_p);
+    ScratchPlan sp;
+    auto colidx = sp.take<int>(nc), maps = sp.take<int>(nc);
+    auto centre = sp.take<double>(nc + 1), zmean = sp.take<double>(nc), zsd = sp.take<double>(nc);
+    auto U = sp.take<double>((int64_t)np * np + 1), amean = sp.take<double>(nall + 1), asd = sp.take<double>(nall + 1);
+    auto groups = sp.take<PcaGroup>(max_groups);
+    auto S = sp.take<double>((int64_t)max_groups * 16 * 256), part = sp.take<double>(sc.part_cap);
+    GD_TRY(sp.get(ctx));
+    sc.colidx = colidx, sc.maps = maps, sc.centre = centre, sc.zmean = zmean, sc.zsd = zsd, sc.U = U;
+    sc.amean = amean, sc.asd = asd, sc.groups = groups, sc.S = S, sc.part = part;
     return GD_OK;
 }
 
@@ -326,10 +319,8 @@ int pca_check(gd_ctx* ctx, const int32_t* cols, int32_t n, const int32_t* maps) 
     GD_REQUIRE(ctx && cols && maps, "null argument");
     GD_REQUIRE(ctx->cols && ctx->N > 0, "no samples uploaded (empty row range)");
     GD_REQUIRE(n >= 1 && n <= ctx->n, "number of PCA columns out of range (1..uploaded columns)");
-    for (int i = 0; i < n; ++i) {
-        GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n, "PCA column index out of range");
-        GD_REQUIRE(maps[i] >= 0 && maps[i] <= 2, "PCA map must be 0 (N), 1 (L) or 2 (M)");
-    }
+    GD_REQUIRE_SAMPLE_COLUMNS(cols, n);
+    for (int i = 0; i < n; ++i) GD_REQUIRE(maps[i] >= 0 && maps[i] <= 2, "PCA map must be 0 (N), 1 (L) or 2 (M)");
     return GD_OK;
 }
 

@@ -230,42 +230,38 @@ int gd_select_samples(gd_ctx* ctx, const gd_selection* sel, int64_t* count_out) 
     const bool host_mask = sel->row_kind == GD_SEL_MASK_U8 && !on_device;
     const bool host_list = sel->row_kind == GD_SEL_ROWS_I32 && !on_device;
     const int nb = (int)((N + GD_SEL_TILE - 1) / GD_SEL_TILE);
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_map = take((int64_t)p.colmap.size() * 4), o_mask = take(host_mask ? N : 0),
-                  o_cnt = take(scan ? ((int64_t)nb + 1) * 8 : 0), o_rows = take(scan ? N * 4 : (host_list ? p.K * 4 : 0)),
-                  o_app = take(p.append_host && !p.contiguous ? N * 8 : 0);
+    ScratchPlan sp;
+    auto b_map = sp.take<int32_t>((int64_t)p.colmap.size());
+    auto b_mask = sp.take<unsigned char>(host_mask ? N : 0);
+    auto b_cnt = sp.take<long long>(scan ? (int64_t)nb + 1 : 0);
+    auto b_rows = sp.take<int32_t>(scan ? N : (host_list ? p.K : 0));
+    auto b_app = sp.take<double>(p.append_host && !p.contiguous ? N : 0);
     const int32_t* d_rows = nullptr;
     const int32_t* d_colmap = nullptr;
     double* d_append = nullptr;
     int64_t K = p.K;
     if (!p.contiguous) {
-        char* base = (char*)gd_scratch2(ctx, off);
-        if (!base) return GD_ERR_NOMEM;
-        d_colmap = (const int32_t*)(base + o_map);
-        d_append = (double*)(base + o_app);
-        GD_TRY(gd_h2d(ctx, base + o_map, p.colmap.data(), p.colmap.size() * 4));
+        GD_TRY(sp.get2(ctx));
+        d_colmap = b_map;
+        d_append = b_app;
+        GD_TRY(gd_h2d(ctx, b_map, p.colmap.data(), p.colmap.size() * 4));
         if (scan) {
             const unsigned char* d_mask = nullptr;
             if (sel->row_kind == GD_SEL_MASK_U8) {
                 d_mask = (const unsigned char*)sel->rows;
                 if (host_mask) {
-                    GD_TRY(gd_h2d(ctx, base + o_mask, sel->rows, (size_t)N));
-                    d_mask = (const unsigned char*)(base + o_mask);
+                    GD_TRY(gd_h2d(ctx, b_mask, sel->rows, (size_t)N));
+                    d_mask = b_mask;
                 }
             }
-            GD_TRY(build_row_list(ctx, d_mask, sel->thr, (long long*)(base + o_cnt), nb, (int32_t*)(base + o_rows), &K));
-            d_rows = (const int32_t*)(base + o_rows);
+            GD_TRY(build_row_list(ctx, d_mask, sel->thr, b_cnt, nb, b_rows, &K));
+            d_rows = b_rows;
             GD_REQUIRE(K > 0, "gd_select_samples: no rows selected");
             GD_REQUIRE(sel->weight_kind != GD_SEL_W_REPLACE || sel->K == K,
                        "gd_select_samples: the number of new weights is not the number of rows selected");
         } else if (host_list) {
-            GD_TRY(gd_h2d(ctx, base + o_rows, sel->rows, (size_t)(p.K * 4)));
-            d_rows = (const int32_t*)(base + o_rows);
+            GD_TRY(gd_h2d(ctx, b_rows, sel->rows, (size_t)(p.K * 4)));
+            d_rows = b_rows;
         } else {
             d_rows = (const int32_t*)sel->rows;
         }

@@ -1774,20 +1774,18 @@ int gd_kde_lag_sums_2d(gd_ctx* ctx, int32_t coli, int32_t colj, const double* ki
     int nblk = (8 * ctx->cu_count + nlags - 1) / nlags;
     if (nblk < 8) nblk = 8;
     if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-    const int64_t o_l = ((int64_t)nlags * nblk * 8 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch(ctx, o_l + nlags * 8);
-    if (!base) return GD_ERR_NOMEM;
-    double* part = (double*)base;
-    int64_t* d_lags = (int64_t*)(base + o_l);
+    ScratchPlan sp;
+    auto part = sp.take<double>((int64_t)nlags * nblk);
+    auto d_lags = sp.tail<int64_t>(nlags);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_lags, lags, (size_t)nlags * 8));
     const double* x = ctx->cols + (int64_t)coli * ctx->ld;
     const double* y = ctx->cols + (int64_t)colj * ctx->ld;
     const dim3 grid(nblk, nlags);
     // kinv3 = {K00, K01 + K10, K11} of inv(cov)/h^2
-    if (ctx->w)
-        k_kde_lag_2d<true><<<grid, 256, 0, ctx->stream>>>(x, y, ctx->w, ctx->N, kinv3[0], kinv3[1], kinv3[2], d_lags, part);
-    else
-        k_kde_lag_2d<false><<<grid, 256, 0, ctx->stream>>>(x, y, nullptr, ctx->N, kinv3[0], kinv3[1], kinv3[2], d_lags, part);
+    gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+        k_kde_lag_2d<HW.value><<<grid, 256, 0, ctx->stream>>>(x, y, ctx->w, ctx->N, kinv3[0], kinv3[1], kinv3[2], d_lags, part);
+    });
     GD_KERNEL_CHECK();
     std::vector<double> h((size_t)nlags * nblk);
     GD_TRY(gd_fetch(ctx, h.data(), part, h.size() * 8));
@@ -1802,7 +1800,7 @@ int gd_kde_lag_sums_2d(gd_ctx* ctx, int32_t coli, int32_t colj, const double* ki
 
 int gd_weight_stats(gd_ctx* ctx, int64_t lo, int64_t hi, double thresh, double* out4) {
     GD_REQUIRE(ctx && out4, "null argument");
-    GD_REQUIRE(ctx->cols && lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
+    GD_REQUIRE_ROWS(lo, hi);
     if (!ctx->w) {
         const double cnt = (double)(hi - lo);
         out4[0] = cnt, out4[1] = 1.0, out4[2] = cnt, out4[3] = (1.0 > thresh) ? cnt : 0.0;
@@ -1833,20 +1831,17 @@ static int col_stats_device(gd_ctx* ctx, const int32_t* d_colidx, int ncols, int
     {
         constexpr int G = 8;
         const dim3 ggrid(nblk, (ncols + G - 1) / G);
-        if (ctx->w)
-            k_col_pass1g<true, G><<<ggrid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_colidx, ncols, ctx->w, lo, hi, d_part);
-        else
-            k_col_pass1g<false, G><<<ggrid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_colidx, ncols, nullptr, lo, hi, d_part);
+        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+            k_col_pass1g<HW.value, G><<<ggrid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_colidx, ncols, ctx->w, lo, hi, d_part);
+        });
     }
     GD_KERNEL_CHECK();
     k_col_fin1<<<ncols, 256, 0, ctx->stream>>>(d_part, nblk, d_res);
     GD_KERNEL_CHECK();
     if (d_out) {
-        if (ctx->w)
-            k_col_pass2<true><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_colidx, ctx->w, lo, hi, d_res, d_part);
-        else
-            k_col_pass2<false><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_colidx, nullptr, lo, hi, d_res,
-                                                              d_part);
+        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+            k_col_pass2<HW.value><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_colidx, ctx->w, lo, hi, d_res, d_part);
+        });
         GD_KERNEL_CHECK();
         k_col_fin2<<<ncols, 256, 0, ctx->stream>>>(d_part, nblk, d_res, d_out);
         GD_KERNEL_CHECK();
@@ -1856,7 +1851,7 @@ static int col_stats_device(gd_ctx* ctx, const int32_t* d_colidx, int ncols, int
 
 int gd_col_stats(gd_ctx* ctx, int64_t lo, int64_t hi, double* out) {
     GD_REQUIRE(ctx && out, "null argument");
-    GD_REQUIRE(ctx->cols && lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
+    GD_REQUIRE_ROWS(lo, hi);
     const int n = (int)ctx->n;
     const int64_t bytes = ((int64_t)n * NBLK_STREAM * 4 + (int64_t)n * 8) * 8;
     double* base = (double*)gd_scratch(ctx, bytes);
@@ -1874,22 +1869,20 @@ int gd_col_stats(gd_ctx* ctx, int64_t lo, int64_t hi, double* out) {
 int gd_col_minmax(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, int64_t hi, int32_t cond_col,
                   double cond_below, double* out) {
     GD_REQUIRE(ctx && cols && out && ncols > 0, "bad argument");
-    GD_REQUIRE(ctx->cols && lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
+    GD_REQUIRE_ROWS(lo, hi);
     GD_REQUIRE(cond_col < ctx->n + GD_EXTRA_COLS, "condition column out of range");
-    for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_COLUMNS(cols, ncols);
     const int nblk = NBLK_STREAM;
-    const int64_t idx_bytes = ((int64_t)ncols * 4 + 255) / 256 * 256;
-    char* base = (char*)gd_scratch(ctx, idx_bytes + (int64_t)ncols * nblk * 2 * 8);
-    if (!base) return GD_ERR_NOMEM;
-    int32_t* d_idx = (int32_t*)base;
-    double* d_part = (double*)(base + idx_bytes);
+    ScratchPlan sp;
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_part = sp.tail<double>((int64_t)ncols * nblk * 2);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
     dim3 grid(nblk, ncols);
-    if (cond_col >= 0)
-        k_col_minmax<true><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->cols + (int64_t)cond_col * ctx->ld,
-                                                          cond_below, lo, hi, d_part);
-    else
-        k_col_minmax<false><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, 0.0, lo, hi, d_part);
+    gd_by_flag(cond_col >= 0, [&](auto HC) {
+        k_col_minmax<HC.value><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, HC.value ? ctx->cols + (int64_t)cond_col * ctx->ld : nullptr,
+                                                              HC.value ? cond_below : 0.0, lo, hi, d_part);
+    });
     GD_KERNEL_CHECK();
     std::vector<double> h((size_t)ncols * nblk * 2);
     GD_TRY(gd_fetch(ctx, h.data(), d_part, h.size() * 8));
@@ -1908,14 +1901,9 @@ int gd_col_minmax(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, i
 int gd_cov(gd_ctx* ctx, const int32_t* cols, int32_t m, int64_t lo, int64_t hi, double* means_out, double* cov_out,
            double* norm_out, double* minmax_out) {
     GD_REQUIRE(ctx && cols && means_out && cov_out && norm_out && m > 0, "bad argument");
-    GD_REQUIRE(ctx->cols && lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
-    for (int i = 0; i < m; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_ROWS(lo, hi);
+    GD_REQUIRE_COLUMNS(cols, m);
     const int64_t rows = hi - lo;
-    auto take_init = [](int64_t& off, int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
     double* d_res = nullptr;
     double* d_cov = nullptr;
     const bool slab = (m <= 208) && !getenv("GDHIP_COV_TILE");
@@ -1949,20 +1937,16 @@ int gd_cov(gd_ctx* ctx, const int32_t* cols, int32_t m, int64_t lo, int64_t hi, 
         int64_t rows_per_chunk = (rows + nblk - 1) / nblk;
         rows_per_chunk = (rows_per_chunk + KS - 1) / KS * KS;
         nblk = (int)((rows + rows_per_chunk - 1) / rows_per_chunk);
-        int64_t off = 0;
-        const int64_t o_part1 = take_init(off, (int64_t)m * NBLK_STREAM * 4 * 8), o_res = take_init(off, (int64_t)m * 4 * 8),
-                      o_idx = take_init(off, (int64_t)m * 4), o_cpart = take_init(off, (int64_t)nblk * T * 256 * 8),
-                      o_cov = take_init(off, (int64_t)m * m * 8), o_mm = take_init(off, (int64_t)nblk * m * 2 * 8),
-                      o_S = take_init(off, (int64_t)mc * mc * 8);
-        char* base = (char*)gd_scratch(ctx, off);
-        if (!base) return GD_ERR_NOMEM;
-        double* d_part1 = (double*)(base + o_part1);
-        d_res = (double*)(base + o_res);
-        int32_t* d_idx = (int32_t*)(base + o_idx);
-        double* d_cpart = (double*)(base + o_cpart);
-        d_cov = (double*)(base + o_cov);
-        double* d_mm = (double*)(base + o_mm);
-        double* d_S = (double*)(base + o_S);
+        ScratchPlan sp;
+        auto d_part1 = sp.take<double>((int64_t)m * NBLK_STREAM * 4);
+        auto b_res = sp.take<double>((int64_t)m * 4);
+        auto d_idx = sp.take<int32_t>(m);
+        auto d_cpart = sp.take<double>((int64_t)nblk * T * 256);
+        auto b_cov = sp.take<double>((int64_t)m * m);
+        auto d_mm = sp.take<double>((int64_t)nblk * m * 2);
+        auto d_S = sp.take<double>((int64_t)mc * mc);
+        GD_TRY(sp.get(ctx));
+        d_res = b_res, d_cov = b_cov;
         GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)m * 4));
         if (onepass) {
             k_col_shift<<<m, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, lo, hi, d_res);
@@ -2027,30 +2011,24 @@ int gd_cov(gd_ctx* ctx, const int32_t* cols, int32_t m, int64_t lo, int64_t hi, 
     rows_per_chunk = (rows_per_chunk + CRB - 1) / CRB * CRB;
     nchunks = (int)((rows + rows_per_chunk - 1) / rows_per_chunk);
     // scratch layout
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { return take_init(off, bytes); };
-    const int64_t o_part1 = take((int64_t)m * NBLK_STREAM * 4 * 8), o_res = take((int64_t)m * 4 * 8),
-                  o_idx = take((int64_t)m * 4), o_tiles = take((int64_t)ntp * 8),
-                  o_cpart = take((int64_t)ntp * nchunks * CT * CT * 8), o_cov = take((int64_t)m * m * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    double* d_part1 = (double*)(base + o_part1);
-    d_res = (double*)(base + o_res);
-    int32_t* d_idx = (int32_t*)(base + o_idx);
-    int2* d_tiles = (int2*)(base + o_tiles);
-    double* d_cpart = (double*)(base + o_cpart);
-    d_cov = (double*)(base + o_cov);
+    ScratchPlan sp;
+    auto d_part1 = sp.take<double>((int64_t)m * NBLK_STREAM * 4);
+    auto b_res = sp.take<double>((int64_t)m * 4);
+    auto d_idx = sp.take<int32_t>(m);
+    auto d_tiles = sp.take<int2>(ntp);
+    auto d_cpart = sp.take<double>((int64_t)ntp * nchunks * CT * CT);
+    auto b_cov = sp.take<double>((int64_t)m * m);
+    GD_TRY(sp.get(ctx));
+    d_res = b_res, d_cov = b_cov;
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)m * 4));
     GD_TRY(gd_h2d(ctx, d_tiles, tiles.data(), (size_t)ntp * 8));
     int rc = col_stats_device(ctx, d_idx, m, lo, hi, d_res, d_part1, nullptr);
     if (rc) return rc;
     dim3 grid(nchunks, ntp);
-    if (ctx->w)
-        k_cov_tile<true><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, ctx->w, lo, hi,
-                                                         rows_per_chunk, d_tiles, d_cpart);
-    else
-        k_cov_tile<false><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, nullptr, lo, hi,
-                                                          rows_per_chunk, d_tiles, d_cpart);
+    gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+        k_cov_tile<HW.value><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, ctx->w, lo, hi, rows_per_chunk, d_tiles,
+                                                            d_cpart);
+    });
     GD_KERNEL_CHECK();
     k_cov_fin<<<dim3((CT * CT + 255) / 256, ntp), 256, 0, ctx->stream>>>(d_cpart, nchunks, d_tiles, m, d_res, d_cov);
     GD_KERNEL_CHECK();
@@ -2131,42 +2109,30 @@ static int quantiles_linear(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int
     int nblk2 = (8 * ctx->cu_count + ncols - 1) / ncols;
     if (nblk2 < 8) nblk2 = 8;
     if (nblk2 > 2 * ctx->cu_count) nblk2 = 2 * ctx->cu_count;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_st = take((int64_t)ncols * sizeof(QState)), o_ql = take((int64_t)ncols * sizeof(QLin)),
-                  o_idx = take((int64_t)ncols * 4), o_out = take((int64_t)ncols * k * 8),
-                  o_cnt = take((int64_t)ncols * QK_MAX * 4 + 256), o_lk = take((int64_t)ncols * QK_MAX * QCAP * 8),
-                  o_lw = take((int64_t)ncols * QK_MAX * QCAP * 8), o_part = take((int64_t)ncols * nblk * nb * (hw ? 8 : 4)),
-                  o_tot = take((int64_t)ncols * nb * 8), o_pmean = take((int64_t)ncols * 8),
-                  o_ppart = take((int64_t)ncols * nblk * QP_LAGS * 8), o_pout = take((int64_t)ncols * QP_LAGS * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
+    ScratchPlan sp;
+    auto d_st = sp.take<QState>(ncols);
+    auto d_ql = sp.take<QLin>(ncols);
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_out = sp.take<double>((int64_t)ncols * k);
+    auto d_cnt = sp.take<int>((int64_t)ncols * QK_MAX + 64);  // the overflow flag sits behind the counters
+    auto d_lk = sp.take<unsigned long long>((int64_t)ncols * QK_MAX * QCAP);
+    auto d_lw = sp.take<double>((int64_t)ncols * QK_MAX * QCAP);
+    auto d_part = sp.take<char>((int64_t)ncols * nblk * nb * (hw ? 8 : 4));
+    auto d_tot = sp.take<double>((int64_t)ncols * nb);
+    auto d_pmean = sp.take<double>(ncols);
+    auto d_ppart = sp.take<double>((int64_t)ncols * nblk * QP_LAGS);
+    auto d_pout = sp.take<double>((int64_t)ncols * QP_LAGS);
+    GD_TRY(sp.get(ctx));
     // whole columns of the sample set: the fused pass (tiles; bucket columns for the later passes; the lag probe on request)
     bool whole = lo == 0 && hi == ctx->N && !getenv("GDHIP_QLIN_UNFUSED");
     for (int c = 0; whole && c < ncols; ++c) whole = cols[c] < ctx->n;
     unsigned short* bq = whole ? bucket_columns(ctx) : nullptr;
     const bool probe = whole && probe_means && probe_out;
-    double* d_pmean = (double*)(base + o_pmean);
-    double* d_ppart = (double*)(base + o_ppart);
-    double* d_pout = (double*)(base + o_pout);
     if (probe) GD_TRY(gd_h2d(ctx, d_pmean, probe_means, (size_t)ncols * 8));
     if (bq) {  // the columns' buckets are being rewritten: not valid until this call has seen its kernels complete
         std::lock_guard<std::mutex> g(ctx->bq->mu);
         for (int c = 0; c < ncols; ++c) ctx->bq->nb[cols[c]] = 0;
     }
-    QState* d_st = (QState*)(base + o_st);
-    QLin* d_ql = (QLin*)(base + o_ql);
-    int32_t* d_idx = (int32_t*)(base + o_idx);
-    double* d_out = (double*)(base + o_out);
-    int* d_cnt = (int*)(base + o_cnt);
-    unsigned long long* d_lk = (unsigned long long*)(base + o_lk);
-    double* d_lw = (double*)(base + o_lw);
-    void* d_part = base + o_part;
-    double* d_tot = (double*)(base + o_tot);
     GD_TRY(gd_h2d(ctx, d_st, hst.data(), hst.size() * sizeof(QState)));
     GD_TRY(gd_h2d(ctx, d_ql, hql.data(), hql.size() * sizeof(QLin)));
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
@@ -2175,43 +2141,37 @@ static int quantiles_linear(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int
     const size_t lds_tiles = lds + (probe ? (size_t)16 * (128 + QP_LAGS) * 8 : 0);
     // 2^k with 2^k * (sum of all weights) < 2^62 (gd_quantiles_mm checked that the sum is known and positive)
     const double wscale = hw ? ldexp(1.0, 61 - ilogb(ctx->w_sum)) : 1.0;
-#define GD_QLIN(HW)                                                                                                                  \
-    do {                                                                                                                             \
-        if (whole) {                                                                                                                 \
-            if (probe) {                                                                                                             \
-                GD_HIP(hipFuncSetAttribute((const void*)k_qlin_count_tiles<HW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tiles)); \
-                k_qlin_count_tiles<HW, true><<<dim3(nblk, ncols), 1024, lds_tiles, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_ql, \
-                                                                                                 d_part, wscale, bq, d_pmean, d_ppart);  \
-            } else {                                                                                                                 \
-                GD_HIP(hipFuncSetAttribute((const void*)k_qlin_count_tiles<HW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tiles)); \
-                k_qlin_count_tiles<HW, false><<<dim3(nblk, ncols), 1024, lds_tiles, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_ql, \
-                                                                                                  d_part, wscale, bq, nullptr, nullptr); \
-            }                                                                                                                        \
-        } else {                                                                                                                     \
-            GD_HIP(hipFuncSetAttribute((const void*)k_qlin_count<HW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-            k_qlin_count<HW><<<dim3(nblk, ncols), 1024, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, d_ql, d_part, wscale); \
-        }                                                                                                                            \
-        GD_KERNEL_CHECK();                                                                                                           \
-        if (probe) {                                                                                                                 \
-            k_sum_partials_batched<<<dim3(QP_LAGS, ncols), 256, 0, ctx->stream>>>(d_ppart, nblk, QP_LAGS, d_pout);                   \
-            GD_KERNEL_CHECK();                                                                                                       \
-        }                                                                                                                            \
-        k_qlin_reduce<HW><<<dim3(nb / 256, ncols), 256, 0, ctx->stream>>>(d_part, nblk, d_tot, 1.0 / wscale);                        \
-        GD_KERNEL_CHECK();                                                                                                           \
-        k_qlin_scan<HW><<<ncols, 1024, 0, ctx->stream>>>(d_st, d_ql, d_tot);                                                         \
-        GD_KERNEL_CHECK();                                                                                                           \
-        if (bq)                                                                                                                      \
-            k_qlin_collect_bq<HW><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_st, d_ql, bq, d_lk, \
-                                                                               d_lw, d_cnt);                                         \
-        else                                                                                                                         \
-            k_qlin_collect<HW><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, d_st, d_ql, d_lk, d_lw,  \
-                                                                            d_cnt);                                                  \
-    } while (0)
-    if (hw)
-        GD_QLIN(true);
-    else
-        GD_QLIN(false);
-#undef GD_QLIN
+    GD_TRY(gd_by_flag(hw, [&](auto HW) -> int {
+        if (whole) {
+            GD_TRY(gd_by_flag(probe, [&](auto PROBE) -> int {
+                GD_HIP(hipFuncSetAttribute((const void*)k_qlin_count_tiles<HW.value, PROBE.value>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds_tiles));
+                k_qlin_count_tiles<HW.value, PROBE.value><<<dim3(nblk, ncols), 1024, lds_tiles, ctx->stream>>>(
+                    ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_ql, d_part, wscale, bq, PROBE.value ? d_pmean.ptr() : nullptr,
+                    PROBE.value ? d_ppart.ptr() : nullptr);
+                return GD_OK;
+            }));
+        } else {
+            GD_HIP(hipFuncSetAttribute((const void*)k_qlin_count<HW.value>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            k_qlin_count<HW.value><<<dim3(nblk, ncols), 1024, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, d_ql, d_part, wscale);
+        }
+        GD_KERNEL_CHECK();
+        if (probe) {
+            k_sum_partials_batched<<<dim3(QP_LAGS, ncols), 256, 0, ctx->stream>>>(d_ppart, nblk, QP_LAGS, d_pout);
+            GD_KERNEL_CHECK();
+        }
+        k_qlin_reduce<HW.value><<<dim3(nb / 256, ncols), 256, 0, ctx->stream>>>(d_part, nblk, d_tot, 1.0 / wscale);
+        GD_KERNEL_CHECK();
+        k_qlin_scan<HW.value><<<ncols, 1024, 0, ctx->stream>>>(d_st, d_ql, d_tot);
+        GD_KERNEL_CHECK();
+        if (bq)
+            k_qlin_collect_bq<HW.value><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_st, d_ql, bq, d_lk,
+                                                                                     d_lw, d_cnt);
+        else
+            k_qlin_collect<HW.value><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, d_st, d_ql, d_lk, d_lw,
+                                                                                  d_cnt);
+        return GD_OK;
+    }));
     GD_KERNEL_CHECK();
     k_qsel_finish<<<dim3(ncols, QK_MAX), 1024, 0, ctx->stream>>>(d_st, d_lk, d_lw, d_cnt, k, 8, d_out, d_cnt + (int64_t)ncols * QK_MAX,
                                                                  hw || getenv("GDHIP_QSEL_WALK") ? 0 : 1);
@@ -2240,7 +2200,7 @@ int gd_quantiles_mm_probe(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64
     GD_REQUIRE(ctx && cols && targets && out && ncols > 0, "bad argument");
     if (probe_done) *probe_done = 0;
     GD_REQUIRE(k > 0 && k <= QK_MAX, "at most 16 quantiles per call");
-    GD_REQUIRE(ctx->cols && lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
+    GD_REQUIRE_ROWS(lo, hi);
     bool linear = minmax != nullptr && getenv("GDHIP_QSEL_RADIX") == nullptr;
     // the expected length of a live bucket's list is rows / buckets times the peak-to-mean density ratio (about 4 for a
     // Gaussian over its sampled range); beyond these row counts the lists would overflow QCAP
@@ -2253,7 +2213,7 @@ int gd_quantiles_mm_probe(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64
         if (!(b > a) || !std::isfinite(a) || !std::isfinite(b) || !std::isfinite((double)QLIN_NB_U / (b - a))) linear = false;
     }
     if (linear) {
-        for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+        GD_REQUIRE_COLUMNS(cols, ncols);
         int overflowed = 0;
         const bool want_probe = probe_means && probe_out && probe_done && lo == 0 && hi == ctx->N && !getenv("GDHIP_QLIN_UNFUSED");
         const int rc = quantiles_linear(ctx, cols, ncols, lo, hi, targets, k, minmax, out, &overflowed, want_probe ? probe_means : nullptr,
@@ -2272,8 +2232,8 @@ int gd_quantiles(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, in
                  int32_t k, double* out) {
     GD_REQUIRE(ctx && cols && targets && out && ncols > 0, "bad argument");
     GD_REQUIRE(k > 0 && k <= QK_MAX, "at most 16 quantiles per call");
-    GD_REQUIRE(ctx->cols && lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
-    for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_ROWS(lo, hi);
+    GD_REQUIRE_COLUMNS(cols, ncols);
     std::vector<QState> hst((size_t)ncols);
     memset(hst.data(), 0, hst.size() * sizeof(QState));
     for (int c = 0; c < ncols; ++c) {
@@ -2281,25 +2241,15 @@ int gd_quantiles(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, in
         hst[c].nuniq = 1;
         for (int t = 0; t < k; ++t) hst[c].target[t] = targets[(size_t)c * k + t];
     }
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_st = take((int64_t)ncols * sizeof(QState)), o_h = take((int64_t)ncols * QK_MAX * 256 * 8),
-                  o_idx = take((int64_t)ncols * 4), o_out = take((int64_t)ncols * k * 8),
-                  o_cnt = take((int64_t)ncols * QK_MAX * 4 + 256), o_lk = take((int64_t)ncols * QK_MAX * QCAP * 8),
-                  o_lw = take((int64_t)ncols * QK_MAX * QCAP * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    QState* d_st = (QState*)(base + o_st);
-    double* d_h = (double*)(base + o_h);
-    int32_t* d_idx = (int32_t*)(base + o_idx);
-    double* d_out = (double*)(base + o_out);
-    int* d_cnt = (int*)(base + o_cnt);
-    unsigned long long* d_lk = (unsigned long long*)(base + o_lk);
-    double* d_lw = (double*)(base + o_lw);
+    ScratchPlan sp;
+    auto d_st = sp.take<QState>(ncols);
+    auto d_h = sp.take<double>((int64_t)ncols * QK_MAX * 256);
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_out = sp.take<double>((int64_t)ncols * k);
+    auto d_cnt = sp.take<int>((int64_t)ncols * QK_MAX + 64);  // the overflow flag sits behind the counters
+    auto d_lk = sp.take<unsigned long long>((int64_t)ncols * QK_MAX * QCAP);
+    auto d_lw = sp.take<double>((int64_t)ncols * QK_MAX * QCAP);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_st, hst.data(), hst.size() * sizeof(QState)));
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
     GD_HIP(hipMemsetAsync(d_h, 0, (size_t)ncols * QK_MAX * 256 * 8, ctx->stream));
@@ -2310,11 +2260,9 @@ int gd_quantiles(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, in
     if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
     auto radix_pass = [&](int pass) -> int {
         dim3 grid(nblk, ncols);
-        if (ctx->w)
-            k_qsel_pass<true><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, pass, d_st, d_h);
-        else
-            k_qsel_pass<false><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, lo, hi, pass, d_st,
-                                                               d_h);
+        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+            k_qsel_pass<HW.value><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, pass, d_st, d_h);
+        });
         GD_KERNEL_CHECK();
         k_qsel_scan<<<ncols, 256, 0, ctx->stream>>>(d_st, d_h, ncols, pass);
         GD_KERNEL_CHECK();
@@ -2328,12 +2276,9 @@ int gd_quantiles(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, in
     GD_HIP(hipMemsetAsync(d_cnt, 0, (size_t)ncols * QK_MAX * 4 + 256, ctx->stream));
     {
         dim3 grid(nblk, ncols);
-        if (ctx->w)
-            k_qsel_collect<true><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, P, d_st, d_lk, d_lw,
-                                                                  d_cnt);
-        else
-            k_qsel_collect<false><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, lo, hi, P, d_st, d_lk,
-                                                                   d_lw, d_cnt);
+        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+            k_qsel_collect<HW.value><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, P, d_st, d_lk, d_lw, d_cnt);
+        });
         GD_KERNEL_CHECK();
     }
     k_qsel_finish<<<dim3(ncols, QK_MAX), 1024, 0, ctx->stream>>>(d_st, d_lk, d_lw, d_cnt, k, P, d_out, d_cnt + (int64_t)ncols * QK_MAX,
@@ -2363,43 +2308,30 @@ int gd_autocov_lags_range_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols,
                                 int64_t row_hi, int64_t k0, int32_t nlags, double* out) {
     GD_REQUIRE(ctx && cols && means && out && nlags > 0 && ncols > 0, "bad argument");
     GD_REQUIRE(ctx->cols && k0 >= 0, "bad lag / no samples");
-    GD_REQUIRE(row_lo >= 0 && row_hi <= ctx->N && row_lo < row_hi, "bad row range");
+    GD_REQUIRE_ROWS(row_lo, row_hi);
     const int64_t NR = row_hi - row_lo;
-    for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_COLUMNS(cols, ncols);
     int nblk = (8 * ctx->cu_count + ncols - 1) / ncols;
     if (nblk < 16) nblk = 16;
     if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_part = take((int64_t)ncols * nblk * AL * 8), o_out = take((int64_t)ncols * AL * 8),
-                  o_idx = take((int64_t)ncols * 4), o_mean = take((int64_t)ncols * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    double* part = (double*)(base + o_part);
-    double* d_out = (double*)(base + o_out);
-    int32_t* d_idx = (int32_t*)(base + o_idx);
-    double* d_mean = (double*)(base + o_mean);
+    ScratchPlan sp;
+    auto part = sp.take<double>((int64_t)ncols * nblk * AL);
+    auto d_out = sp.take<double>((int64_t)ncols * AL);
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_mean = sp.take<double>(ncols);
+    GD_TRY(sp.get(ctx));
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
     GD_TRY(gd_h2d(ctx, d_mean, means, (size_t)ncols * 8));
     std::vector<double> h((size_t)ncols * AL);
     for (int32_t done = 0; done < nlags;) {
         const dim3 grid(nblk, ncols);
         const int NL = (nlags - done <= 8) ? 8 : AL;  // short first probe: uncorrelated chains stop at lag 1
-        if (NL == 8) {
-            if (ctx->w)
-                k_autocov<true, 8><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, row_lo, NR, d_mean, k0 + done, part);
+        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+            if (NL == 8)
+                k_autocov<HW.value, 8><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, row_lo, NR, d_mean, k0 + done, part);
             else
-                k_autocov<false, 8><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, row_lo, NR, d_mean, k0 + done, part);
-        } else {
-            if (ctx->w)
-                k_autocov<true, AL><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, row_lo, NR, d_mean, k0 + done, part);
-            else
-                k_autocov<false, AL><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, row_lo, NR, d_mean, k0 + done, part);
-        }
+                k_autocov<HW.value, AL><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, row_lo, NR, d_mean, k0 + done, part);
+        });
         GD_KERNEL_CHECK();
         k_sum_partials_batched<<<dim3(NL, ncols), 256, 0, ctx->stream>>>(part, nblk, NL, d_out);
         GD_KERNEL_CHECK();
@@ -2421,7 +2353,7 @@ int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
                           int32_t nlags, double* out) {
     GD_REQUIRE(ctx && cols && inv4s2 && lags && out && nlags > 0 && nlags <= 64 && ncols > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
-    for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_COLUMNS(cols, ncols);
     for (int i = 0; i < nlags; ++i) GD_REQUIRE(lags[i] > 0 && lags[i] < ctx->N, "lag out of range");
     const bool multi = nlags <= KDE_LAG_MAX && getenv("GDHIP_KDE_LAG_SINGLE") == nullptr;
     int per_cu = 8;  // blocks of 256 threads per CU (GDHIP_KDE_LAG_BLOCKS_PER_CU: tuning knob)
@@ -2429,20 +2361,12 @@ int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
     int nblk = multi ? (per_cu * ctx->cu_count + ncols - 1) / ncols : (8 * ctx->cu_count + ncols * nlags - 1) / (ncols * nlags);
     if (nblk < 8) nblk = 8;
     if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_part = take((int64_t)ncols * (multi ? KDE_LAG_MAX : nlags) * nblk * 8), o_lags = take((int64_t)nlags * 8),
-                  o_idx = take((int64_t)ncols * 4), o_c = take((int64_t)ncols * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    double* part = (double*)(base + o_part);
-    int64_t* d_lags = (int64_t*)(base + o_lags);
-    int32_t* d_idx = (int32_t*)(base + o_idx);
-    double* d_c = (double*)(base + o_c);
+    ScratchPlan sp;
+    auto part = sp.take<double>((int64_t)ncols * (multi ? KDE_LAG_MAX : nlags) * nblk);
+    auto d_lags = sp.take<int64_t>(nlags);
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_c = sp.take<double>(ncols);
+    GD_TRY(sp.get(ctx));
     // the N_eff lag set (five lags from N/2, one or two short ones): every sample read once
     int order[KDE_LAG_MAX];
     int nf = 0, nn = 0;
@@ -2474,28 +2398,21 @@ int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
     if (multi) {
         const dim3 grid(nblk, ncols);
         if (folded) {
-#define KDE_FOLDED(W, NNV)                                                                                           \
-    k_kde_lag_folded<W, 5, NNV><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c, d_lags, part)
-            if (ctx->w) {
-                if (nn == 1) KDE_FOLDED(true, 1); else KDE_FOLDED(true, 2);
-            } else {
-                if (nn == 1) KDE_FOLDED(false, 1); else KDE_FOLDED(false, 2);
-            }
-#undef KDE_FOLDED
+            gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+                gd_by_flag(nn == 1, [&](auto ONE) {
+                    k_kde_lag_folded<HW.value, 5, ONE.value ? 1 : 2><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c,
+                                                                                                    d_lags, part);
+                });
+            });
         } else
-#define KDE_LAUNCH(NLV)                                                                                                 \
-    case NLV:                                                                                                           \
-        if (ctx->w)                                                                                                     \
-            k_kde_lag_multi<true, NLV><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c,   \
-                                                                      d_lags, part);                                    \
-        else                                                                                                            \
-            k_kde_lag_multi<false, NLV><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, ctx->N, d_c, \
-                                                                       d_lags, part);                                   \
-        break;
-        switch (nlags) {
-            KDE_LAUNCH(1) KDE_LAUNCH(2) KDE_LAUNCH(3) KDE_LAUNCH(4) KDE_LAUNCH(5) KDE_LAUNCH(6) KDE_LAUNCH(7) KDE_LAUNCH(8)
-        }
+            gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+#define KDE_LAUNCH(NLV) \
+    case NLV: k_kde_lag_multi<HW.value, NLV><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c, d_lags, part); break;
+                switch (nlags) {
+                    KDE_LAUNCH(1) KDE_LAUNCH(2) KDE_LAUNCH(3) KDE_LAUNCH(4) KDE_LAUNCH(5) KDE_LAUNCH(6) KDE_LAUNCH(7) KDE_LAUNCH(8)
+                }
 #undef KDE_LAUNCH
+            });
         GD_KERNEL_CHECK();
         std::vector<double> h((size_t)ncols * nblk * KDE_LAG_MAX);
         GD_TRY(gd_fetch(ctx, h.data(), part, h.size() * 8));
@@ -2509,10 +2426,9 @@ int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
         return GD_OK;
     }
     const dim3 grid(nblk, nlags, ncols);
-    if (ctx->w)
-        k_kde_lag<true><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c, d_lags, part);
-    else
-        k_kde_lag<false><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, nullptr, ctx->N, d_c, d_lags, part);
+    gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+        k_kde_lag<HW.value><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c, d_lags, part);
+    });
     GD_KERNEL_CHECK();
     std::vector<double> h((size_t)ncols * nlags * nblk);
     GD_TRY(gd_fetch(ctx, h.data(), part, h.size() * 8));

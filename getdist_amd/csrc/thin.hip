@@ -165,7 +165,7 @@ int gd_weights_integral(gd_ctx* ctx, int32_t* out) {
 int gd_thin_rows(gd_ctx* ctx, int64_t lo, int64_t hi, int64_t factor, int32_t unique_mode, void* d_rows, int64_t capacity,
                  int64_t* count_out) {
     GD_REQUIRE(ctx && d_rows && count_out, "null argument");
-    GD_REQUIRE(ctx->cols && lo >= 0 && hi <= ctx->N && lo < hi, "bad row range");
+    GD_REQUIRE_ROWS(lo, hi);
     GD_REQUIRE(factor >= 1, "Thin factor must be a positive integer");
     GD_REQUIRE(ctx->N < 2147483647LL, "row indices are 32-bit");
     int32_t integral = 0;
@@ -194,29 +194,23 @@ int gd_binary_transitions(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
     GD_REQUIRE(ctx && cols && d_rows && thresholds && counts_out && ncols > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
     GD_REQUIRE(nthr >= 1 && nthr <= MAX_THR, "1..4 thresholds per column");
-    for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_COLUMNS(cols, ncols);
     const int64_t nc = (int64_t)ncols * nthr * 12;
     memset(counts_out, 0, (size_t)nc * 8);
     if (K < 2) return GD_OK;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_idx = take((int64_t)ncols * 4), o_thr = take((int64_t)ncols * nthr * 8), o_cnt = take(nc * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    GD_TRY(gd_h2d(ctx, base + o_idx, cols, (size_t)ncols * 4));
-    GD_TRY(gd_h2d(ctx, base + o_thr, thresholds, (size_t)ncols * nthr * 8));
-    GD_HIP(hipMemsetAsync(base + o_cnt, 0, (size_t)nc * 8, ctx->stream));
+    ScratchPlan sp;
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_thr = sp.take<double>((int64_t)ncols * nthr);
+    auto d_cnt = sp.take<unsigned long long>(nc);
+    GD_TRY(sp.get(ctx));
+    GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
+    GD_TRY(gd_h2d(ctx, d_thr, thresholds, (size_t)ncols * nthr * 8));
+    GD_HIP(hipMemsetAsync(d_cnt, 0, (size_t)nc * 8, ctx->stream));
     int nblk = (int)((K + 255) / 256);
     if (nblk > 512) nblk = 512;
-    k_binary_transitions<<<dim3(nblk, ncols), 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, (const int32_t*)(base + o_idx),
-                                                                    (const int32_t*)d_rows, K, (const double*)(base + o_thr),
-                                                                    nthr, (unsigned long long*)(base + o_cnt));
+    k_binary_transitions<<<dim3(nblk, ncols), 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, (const int32_t*)d_rows, K, d_thr, nthr, d_cnt);
     GD_KERNEL_CHECK();
-    GD_TRY(gd_fetch(ctx, counts_out, base + o_cnt, (size_t)nc * 8));
+    GD_TRY(gd_fetch(ctx, counts_out, d_cnt, (size_t)nc * 8));
     GD_TRY(gd_stream_sync(ctx));
     return GD_OK;
 }
@@ -226,26 +220,20 @@ int gd_thinned_lag_sums(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const d
     GD_REQUIRE(ctx && cols && means && d_rows && out && ncols > 0 && maxoff > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
     GD_REQUIRE(maxoff < 65536 && ncols < 65536, "too many lags / columns");
-    for (int i = 0; i < ncols; ++i) GD_REQUIRE(cols[i] >= 0 && cols[i] < ctx->n + GD_EXTRA_COLS, "column out of range");
+    GD_REQUIRE_COLUMNS(cols, ncols);
     const int nblk = 64;
     const int64_t np = (int64_t)ncols * maxoff * nblk;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const int64_t o_idx = take((int64_t)ncols * 4), o_mean = take((int64_t)ncols * 8), o_part = take(np * 8);
-    char* base = (char*)gd_scratch(ctx, off);
-    if (!base) return GD_ERR_NOMEM;
-    GD_TRY(gd_h2d(ctx, base + o_idx, cols, (size_t)ncols * 4));
-    GD_TRY(gd_h2d(ctx, base + o_mean, means, (size_t)ncols * 8));
-    k_thinned_lag<<<dim3(nblk, maxoff, ncols), 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, (const int32_t*)(base + o_idx),
-                                                                     (const double*)(base + o_mean), (const int32_t*)d_rows, K,
-                                                                     (double*)(base + o_part));
+    ScratchPlan sp;
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_mean = sp.take<double>(ncols);
+    auto d_part = sp.take<double>(np);
+    GD_TRY(sp.get(ctx));
+    GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
+    GD_TRY(gd_h2d(ctx, d_mean, means, (size_t)ncols * 8));
+    k_thinned_lag<<<dim3(nblk, maxoff, ncols), 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, d_mean, (const int32_t*)d_rows, K, d_part);
     GD_KERNEL_CHECK();
     std::vector<double> h((size_t)np);
-    GD_TRY(gd_fetch(ctx, h.data(), base + o_part, (size_t)np * 8));
+    GD_TRY(gd_fetch(ctx, h.data(), d_part, (size_t)np * 8));
     GD_TRY(gd_stream_sync(ctx));
     for (int64_t e = 0; e < (int64_t)ncols * maxoff; ++e) {
         double s = 0;

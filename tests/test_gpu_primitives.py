@@ -1001,3 +1001,35 @@ def test_real_weight_byte_index_binning_sorted_by_stripe(monkeypatch):
     H4 = c.hist2d_prebinned([b16[a] for a, b in pairs], [b16[b] for a, b in pairs], F).to_host((len(pairs), F, F))
     assert np.max(np.abs(H4 - H)) <= 1e-12 * H.max()
     c.close()
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_dct1d_of_device_histograms_against_the_definition(weighted):
+    """gd_dct1d (the histograms normalised to unit sum, then the DCT-II  a_k = 2 sum_n x_n cos(pi k (2n + 1) / 2F)) on the
+    1D histograms of 5 000 rows x 3 columns, against the definition summed in long double.  F = 257: two blocks of
+    coefficients per histogram and an odd tail of the kernel's two-term loop.  Tolerance from the number format: with
+    sum |x_n| = 1 a coefficient carries at most 2 (F + 2) roundings of 2^-53 (F fused multiply-adds, the cosine table,
+    the normalisation), 5.8e-14 at F = 257; 1e-13 is that bound rounded up."""
+    from getdist_amd._lib import Context
+
+    rng = np.random.default_rng(31)
+    N, F = 5000, 257
+    s = rng.standard_normal((N, 3)) * np.array([1.0, 0.3, 4.0])
+    w = rng.exponential(1.0, N) if weighted else None
+    lo, hi = s.min(axis=0), s.max(axis=0)
+    width = (hi - lo) / (F - 1)
+    c = Context(0)
+    try:
+        c.upload(s, w)
+        hist = c.hist1d([0, 1, 2], lo, width, F)
+        got = c.dct1d(hist)
+    finally:
+        c.close()
+    assert np.all(hist.sum(axis=1) > 0)  # (the histograms themselves have their own tests)
+    x = hist.astype(np.longdouble) / hist.astype(np.longdouble).sum(axis=1, keepdims=True)
+    k, n = np.arange(F)[:, None], np.arange(F)[None, :]
+    m = (k * (2 * n + 1)) % (4 * F)  # the angle pi m / 2F, reduced exactly
+    ref = 2 * x @ np.cos(np.longdouble("3.14159265358979323846264338327950288") * m.astype(np.longdouble) / (2 * F)).T
+    err = float(np.max(np.abs(got.astype(np.longdouble) - ref)))
+    print("dct1d max abs error %.3e" % err)
+    assert got.shape == (3, F) and err <= 1e-13
