@@ -168,6 +168,10 @@ SIGNATURES = {
     "gd_download_samples": (C.c_int, [_p, _pd]),
     "gd_select_samples": (C.c_int, [_p, _p, _pi64]),
     "gd_set_weights": (C.c_int, [_p, _pd]),
+    "gd_export_device": (C.c_int, [_p, _p, _pi64]),
+    "gd_export_alloc": (C.c_int, [_i32, _i64, C.POINTER(_p)]),
+    "gd_export_free": (C.c_int, [_i32, _p]),
+    "gd_export_fetch": (C.c_int, [_i32, _p, _p, _i64]),
 }
 
 GD_HISTND_MAXD, GD_HISTND_MAX_BINS = 25, 1 << 25
@@ -250,6 +254,16 @@ class GdSelection(C.Structure):
                 ("append_host", _p), ("new_weights", _p)]
 
 
+class GdExport(C.Structure):
+    """gd_export of gdhip.h"""
+
+    _fields_ = [("row_kind", _i32), ("flags", _i32), ("lo", _i64), ("hi", _i64), ("rows", _p), ("K", _i64), ("thr", _f64),
+                ("mask_col", _i32), ("m", _i32), ("cols", _p), ("base", _p), ("rows_capacity", _i64), ("row_stride", _i64),
+                ("col_stride", _i64), ("dtype", _i32), ("reserved", _i32), ("consumer_stream", _p)]
+
+
+GD_EXP_ROWS_COLUMN_NZ = 5  # gd_export_device: the rows whose value in a resident column is != 0
+
 # gd_select_samples: row kinds, weight kinds, append kinds, flags, rows per tile of the count / placement passes
 GD_SEL_ALL, GD_SEL_RANGE, GD_SEL_MASK_U8, GD_SEL_WEIGHT_GT, GD_SEL_ROWS_I32 = range(5)
 GD_SEL_W_KEEP, GD_SEL_W_UNIT, GD_SEL_W_REPLACE = range(3)
@@ -328,6 +342,37 @@ class DevBuf:
     def from_host(self, arr, offset_bytes=0):
         arr = np.ascontiguousarray(arr)
         self.ctx._check(self.ctx.lib.gd_memcpy_h2d(self.ctx.h, self.ptr + offset_bytes, arr.ctypes.data, arr.nbytes))
+
+
+class ExportBlock:
+    """Device memory that belongs to no Context (gd_export_alloc): what a devarray.DeviceArray owns.  It stays valid across
+    every mutator, re-upload and Context.close(), never enters a context's block cache, and is freed -- with the device
+    index alone -- when the last reference to it goes."""
+
+    def __init__(self, device, nbytes):
+        self.lib, self.device, self.nbytes = load_library(), int(device), int(nbytes)
+        p = _p()
+        rc = self.lib.gd_export_alloc(self.device, self.nbytes, C.byref(p))
+        if rc == GD_ERR_NOMEM:
+            raise MemoryError("no room for a device array of %d bytes on device %d" % (self.nbytes, self.device))
+        if rc != 0:
+            raise GdhipError(rc, "gd_export_alloc(%d bytes) failed" % self.nbytes)
+        self.ptr = p.value
+
+    def fetch(self, out):
+        """the block's first out.nbytes bytes into the C-contiguous host array ``out``"""
+        rc = self.lib.gd_export_fetch(self.device, out.ctypes.data, self.ptr, out.nbytes)
+        if rc != 0:
+            raise GdhipError(rc, "gd_export_fetch failed")
+        return out
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                self.lib.gd_export_free(self.device, self.ptr)
+            self.ptr = None
+        except Exception:
+            pass
 
 
 class Context:
@@ -744,6 +789,71 @@ class Context:
         self._keep = None
         self.N, self.n, self.weighted = int(count.value), int(n_new), weighted
         return self.N
+
+    def export_block(self, nbytes):
+        """device memory for an exported array, owned by the array and not by this context (ExportBlock)"""
+        return ExportBlock(self.device, nbytes)
+
+    def export_device(self, rows=None, cols=None, dest=None, stream=None):
+        """Selected rows of resident columns into a device array (gd_export_device); returns K, the number of rows selected.
+        ``rows``: as select_samples takes them (None, ``("range", lo, hi)``, ``("mask", m)``, ``("weight_gt", thr)``,
+        ``("rows", r)`` / ``("rows", buf, K)``), or ``("nonzero", j)``: the rows where resident column j is != 0.  ``cols``: resident
+        column indices in any order, repeats and spare columns allowed; None: the sample weights (ones for a unit-weight set).
+        ``dest``: a 2-D devarray.DevArray of K rows and len(cols) columns (1 for the weights) in any of the four element
+        types, any non-negative strides; None: nothing is written, the call only counts.  ``stream``: the consumer's stream
+        (None: the call returns when the destination is written; else the two streams are ordered by events and the host
+        does not wait).  ValueError when ``dest`` has fewer rows than are selected, when its elements overlap, and for memory
+        that is not plain device memory of this device; nothing is written then."""
+        ex = GdExport()
+        alive = []
+        kind = "all" if rows is None else rows[0]
+        if kind == "range":
+            ex.row_kind, ex.lo, ex.hi = GD_SEL_RANGE, int(rows[1]), int(rows[2])
+        elif kind in ("mask", "rows"):
+            ex.row_kind = GD_SEL_MASK_U8 if kind == "mask" else GD_SEL_ROWS_I32
+            v = rows[1]
+            if hasattr(v, "ptr"):
+                ex.flags, ex.rows = GD_SEL_ROWS_ON_DEVICE, v.ptr
+                ex.K = int(rows[2]) if kind == "rows" else 0
+            else:
+                if kind == "mask":
+                    v = np.ascontiguousarray(v)
+                    v = v.view(np.uint8) if v.dtype == bool else np.ascontiguousarray(v != 0).view(np.uint8)
+                    if v.shape != (self.N,):
+                        raise ValueError("the row mask must have one entry per sample row")
+                else:
+                    v = _i32arr(v).ravel()
+                    ex.K = v.size
+                alive.append(v)
+                ex.rows = v.ctypes.data
+        elif kind == "weight_gt":
+            ex.row_kind, ex.thr = GD_SEL_WEIGHT_GT, float(rows[1])
+        elif kind == "nonzero":
+            ex.row_kind, ex.mask_col = GD_EXP_ROWS_COLUMN_NZ, int(rows[1])
+        elif kind != "all":
+            raise ValueError("unknown row selection %r" % (kind,))
+        if cols is not None:
+            c = _i32arr(cols).ravel()
+            alive.append(c)
+            ex.cols, ex.m = c.ctypes.data, c.size
+        if dest is not None:
+            if dest.ndim != 2 or dest.shape[1] != (1 if cols is None else len(c)):
+                raise ValueError("the destination must be 2-D with one column per exported column")
+            ex.base, ex.rows_capacity = dest.ptr or None, dest.shape[0]
+            ex.row_stride, ex.col_stride, ex.dtype = dest.strides[0], dest.strides[1], int(dest.dtype)
+        ex.consumer_stream = stream
+        count = C.c_int64()
+        rc = self.lib.gd_export_device(self.h, C.byref(ex), C.byref(count))
+        if rc == GD_DRAW_MORE_ROWS:
+            if dest is None:
+                return int(count.value)
+            raise ValueError("the destination has %d rows, %d are selected" % (dest.shape[0], count.value))
+        if rc == GD_ERR_DECLINED:
+            raise ValueError("out= must be plain device memory with non-negative strides (%s)" % self.lib.gd_last_error(self.h).decode())
+        if rc == GD_ERR_BADARG:
+            raise ValueError(self.lib.gd_last_error(self.h).decode())
+        self._served(rc, [] if dest is None else [dest])
+        return int(count.value)
 
     def set_weights(self, w):
         """Replace only the sample weights of the resident set (gd_set_weights): N host doubles, or None for unit weights."""

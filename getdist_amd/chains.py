@@ -1139,6 +1139,136 @@ class Chains(WeightedSamples):
 
         return self._set_param_attrs(ParSamples(), lambda j, par: col(par.name))
 
+    # ---- the resident samples as device arrays (gd_export_device; not in the reference, which has no device) ---------------
+    _EXPORT_ROWS = ("rows= takes None, a slice with step 1, a boolean mask with one entry per sample, a 1-D integer index array "
+                    "(negative indices count from the end) or a boolean column expression")
+
+    def _export_rows(self, rows):
+        """``rows=`` of getDeviceSamples as (what Context.export_device selects by, the row count K or None where only the
+        device will know it, the boolean expression to evaluate on the device or None)"""
+        N = self.numrows
+        if rows is None:
+            return None, N, None
+        if _is_expr(rows):
+            if not rows.is_bool:
+                raise ValueError("rows= takes a boolean expression (a comparison), not a float one")
+            return None, None, rows
+        if isinstance(rows, slice):
+            lo, hi, step = rows.indices(N)
+            if step != 1:
+                raise ValueError("%s; not a slice with step %d" % (self._EXPORT_ROWS, step))
+            return ("range", lo, max(hi, lo)), max(hi - lo, 0), None
+        if isinstance(rows, (np.ndarray, list, tuple)):
+            a = np.asarray(rows)
+            if a.dtype == bool and a.shape == (N,):
+                return ("mask", a), int(np.count_nonzero(a)), None
+            if a.ndim == 1 and (a.dtype.kind in "iu" or a.size == 0):
+                ix = _where_rows(a, N)  # (numpy's IndexError for an index outside [-N, N))
+                return ("rows", ix), int(ix.size), None
+        what = "%s array of shape %s" % (np.asarray(rows).dtype, np.shape(rows)) if isinstance(rows, (np.ndarray, list, tuple)) \
+            else type(rows).__name__
+        raise ValueError("%s; not a %s" % (self._EXPORT_ROWS, what))
+
+    def _export(self, items, single, rows, dtype, order, out, stream):
+        """getDeviceSamples / getDeviceWeights: ``items`` are resident column indices and column expressions (None: the sample
+        weights).  Expressions go through the spare columns, a group of as many as there are free slots per export call,
+        each group into its column sub-view of the destination."""
+        from . import devarray
+
+        ctx = self.ctx
+        if not hasattr(ctx, "export_device"):
+            raise NotImplementedError("%s has no export_device: the resident samples cannot be handed out as device arrays "
+                                      "by this context" % type(ctx).__name__)
+        if getattr(self, "_column_share", None) is not None:
+            raise MCSamplesError("device arrays need every column resident on one device: this context holds only its rank's "
+                                 "share of the columns")
+        selection, K, mask_expr = self._export_rows(rows)
+        m = 1 if items is None else len(items)
+        exprs = [it for it in (items or []) if _is_expr(it)] + ([] if mask_expr is None else [mask_expr])
+        slots = list(range(ctx.EXTRA_COLS - (1 if any(e.uses_loglikes() for e in exprs) else 0)))
+        dest = None
+        if out is None:
+            code, stream = devarray.dtype_code(dtype), None  # (a result of the library's own is complete on return)
+            if order not in ("C", "F"):
+                raise ValueError("order must be 'C' or 'F'")
+        else:
+            dest = devarray.describe(out)
+            if dest is None:
+                raise TypeError("out= must be a device array: a torch tensor on the GPU or an object with "
+                                "__cuda_array_interface__")
+            if dest.ndim != (1 if single else 2) or (not single and dest.shape[1] != m):
+                raise ValueError("out= must have shape %s, not %s" % ("(K,)" if single else "(K, %d)" % m, dest.shape))
+            if any(s < 0 for s in dest.strides):
+                raise ValueError("out= must be plain device memory with non-negative strides (strides %s)" % (dest.strides,))
+            if K is not None and dest.shape[0] != K:
+                raise ValueError("out= must have %d rows (the rows selected), not %d" % (K, dest.shape[0]))
+            if stream is None:
+                stream = dest.stream
+        if stream is not None:  # (a handle or a torch stream object; handle 0 is the legacy default stream)
+            stream = int(getattr(stream, "cuda_stream", stream)) or devarray.STREAM_LEGACY
+        if mask_expr is not None:
+            selection = ("nonzero", mask_expr.to_column(self, slots.pop(0)))  # 0.0 / 1.0 per row; never fetched
+            K = ctx.export_device(rows=selection, cols=None if items is None else [0])  # a count: nothing is written
+            if dest is not None and dest.shape[0] != K:
+                raise ValueError("out= must have %d rows (the rows selected), not %d" % (K, dest.shape[0]))
+        if dest is None:
+            result = devarray.DeviceArray.allocate(ctx, (K,) if single else (K, m), code, order)
+            dest = result.describe()
+        else:
+            result = out
+        dest = dest.as2d()
+        if K == 0 or m == 0:
+            return result
+        if items is None:
+            ctx.export_device(rows=selection, cols=None, dest=dest, stream=stream)
+            return result
+        start = 0
+        while start < m:
+            free, cols, end = list(slots), [], start
+            while end < m and not (_is_expr(items[end]) and not free):
+                cols.append(items[end].to_column(self, free.pop(0)) if _is_expr(items[end]) else items[end])
+                end += 1
+            part = devarray.DevArray(dest.ptr + start * dest.strides[1] * dest.itemsize, (K, end - start), dest.strides, dest.dtype,
+                                     dest.device, dest.stream, dest.owner)
+            ctx.export_device(rows=selection, cols=cols, dest=part, stream=stream)
+            start = end
+        return result
+
+    def getDeviceSamples(self, params=None, rows=None, dtype=np.float64, order="C", out=None, stream=None):
+        """Rows of parameters (or of expressions of them) as an array in DEVICE memory, without crossing the host: what
+        ``torch.as_tensor(samples.samples[rows][:, cols].astype(dtype)).cuda()`` gives, made on the device.  The result is a
+        snapshot: the sample set may be mutated, re-uploaded or deleted afterwards.  Not in the reference.
+
+        :param params: None (every parameter, in paramNames order) or a list of names, indices, ParamInfo objects and column
+            expressions (getDeviceParams); a single item that is not in a list gives a 1-D result
+        :param rows: None, a slice with step 1, a boolean mask, an integer index array with numpy's semantics, or a boolean
+            column expression (evaluated on the device, never fetched)
+        :param dtype: np.float64, np.float32, np.float16 or "bfloat16": rounded to nearest even in one step from the double
+        :param order: "C" or "F", the layout of a result this call allocates
+        :param out: a device array to write into instead (a torch tensor on the GPU, anything with
+            ``__cuda_array_interface__``): shape (K, m), or (K,) for a single item; any non-negative strides; ITS element type
+            decides the conversion.  Only its elements are written.
+        :param stream: the stream that uses ``out`` (default: the one ``out`` announces); the copy is ordered behind that
+            stream's earlier work and the stream behind the copy, by events.  Without ``out`` it is ignored: the call is
+            complete on return.
+        :return: ``out``, or a :class:`devarray.DeviceArray` that owns its memory (``.torch()``, ``.numpy()``,
+            ``__cuda_array_interface__``)
+        """
+        single = params is not None and not isinstance(params, (list, tuple))
+        wanted = list(range(self.n)) if params is None else [params] if single else list(params)
+        items = []
+        for par in wanted:
+            if _is_expr(par):
+                items.append(par)
+            else:
+                items.append(self._col(int(par) if isinstance(par, np.integer) else par))
+        return self._export(items, single, rows, dtype, order, out, stream)
+
+    def getDeviceWeights(self, rows=None, dtype=np.float64, out=None, stream=None):
+        """The sample weights of the same rows as a 1-D device array (ones for a unit-weight set); arguments as
+        :meth:`getDeviceSamples`."""
+        return self._export(None, True, rows, dtype, "C", out, stream)
+
     def getParamSampleDict(self, ix, want_derived=True):
         """chains.py:1303-1317: {"weight", "loglike", parameter name: value} of sample row ``ix`` (the weight of a unit-weight
         set is 1.0; without loglikes this raises TypeError, as indexing None does in the reference)"""

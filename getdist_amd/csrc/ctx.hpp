@@ -150,6 +150,14 @@ void gd_upload_install(gd_ctx* ctx, double* cols, double* w, unsigned char* w8, 
 int gd_upload_weight_flags(gd_ctx* ctx, const double* w, int64_t N, int64_t ld, unsigned char** w8_out, bool* integral_out,
                            double* wsum_out);
 
+// devinput.hip: what a caller's device array must pass before a kernel may touch it, on the way in (gd_upload_device) and on
+// the way out (gd_export_device): bytes per element of a GD_DT_* code (0: unknown); the description names plain device memory
+// of the context's device inside its allocation; the context's stream waits (by an event, not on the host) for what a
+// caller's stream has been given so far (0: no stream, 1: the legacy default stream, 2: the per-thread stream, else a handle)
+int gd_dtype_bytes(int dtype);
+int gd_check_device_array(gd_ctx* ctx, const char* what, const void* base, int64_t rows, int64_t cols, int64_t rs, int64_t cs, int sz);
+int gd_wait_for_stream(gd_ctx* ctx, void* producer);
+
 int gd_fail(gd_ctx* ctx, int code, const char* fmt, ...);
 void gd_comm_release(gd_ctx* ctx);  // comm.hip
 bool gd_ctx_alive(gd_ctx* ctx);

@@ -179,7 +179,10 @@ __global__ void k_cols_to_rows(const double* __restrict__ cols, int64_t ld, int6
     }
 }
 
-int dtype_bytes(int dtype) {
+}  // namespace
+
+// (the three below are shared with devexport.hip: declared in ctx.hpp)
+int gd_dtype_bytes(int dtype) {
     switch (dtype) {
         case GD_DT_F64: return 8;
         case GD_DT_F32: return 4;
@@ -191,7 +194,7 @@ int dtype_bytes(int dtype) {
 
 // The description (base, shape, strides, element size) names plain device memory of the context's device and stays inside
 // its allocation.  Nothing is launched before every array of a call has passed.
-int check_array(gd_ctx* ctx, const char* what, const void* base, int64_t rows, int64_t cols, int64_t rs, int64_t cs, int sz) {
+int gd_check_device_array(gd_ctx* ctx, const char* what, const void* base, int64_t rows, int64_t cols, int64_t rs, int64_t cs, int sz) {
     if (!base) return gd_fail(ctx, GD_ERR_BADARG, "%s: null pointer", what);
     if (rows <= 0 || cols <= 0) return gd_fail(ctx, GD_ERR_BADARG, "%s: empty shape %lld x %lld", what, (long long)rows, (long long)cols);
     if (rs < 0 || cs < 0)
@@ -223,7 +226,7 @@ int check_array(gd_ctx* ctx, const char* what, const void* base, int64_t rows, i
 }
 
 // the context's stream runs behind everything the producer stream has been given so far; the host does not wait
-int wait_producer(gd_ctx* ctx, void* producer) {
+int gd_wait_for_stream(gd_ctx* ctx, void* producer) {
     if (!producer) return GD_OK;
     hipStream_t s = producer == (void*)1 ? (hipStream_t) nullptr : (hipStream_t)producer;  // 1: the legacy default stream
     hipEvent_t ev = nullptr;
@@ -234,6 +237,8 @@ int wait_producer(gd_ctx* ctx, void* producer) {
     GD_HIP(e);
     return GD_OK;
 }
+
+namespace {
 
 unsigned blocks_for(int64_t items, int per_block, unsigned cap) {
     const int64_t b = (items + per_block - 1) / per_block;
@@ -287,7 +292,7 @@ int device_build(gd_ctx* ctx, const gd_dev_part* parts, int nparts, int dtype, i
                  bool weighted, int64_t N, int64_t ld, void* const* producers, int nproducers, double** cols_out, double** w_out, unsigned char** w8_out,
                  bool* integral_out, double* wsum_out) {
     const int64_t m = (int64_t)keep.size();
-    for (int k = 0; k < nproducers; ++k) GD_TRY(wait_producer(ctx, producers[k]));
+    for (int k = 0; k < nproducers; ++k) GD_TRY(gd_wait_for_stream(ctx, producers[k]));
     GD_HIP(hipMalloc((void**)cols_out, (size_t)(ld * (m + GD_EXTRA_COLS) * 8)));
     double* cols = *cols_out;
     GD_HIP(hipMemsetAsync(cols + ld * m, 0, (size_t)(ld * GD_EXTRA_COLS * 8), ctx->stream));
@@ -343,7 +348,7 @@ int gd_upload_device(gd_ctx* ctx, const gd_dev_part* parts, int32_t nparts, int3
     if (!ctx) return GD_ERR_BADARG;
     GD_REQUIRE(parts && nparts > 0, "gd_upload_device: no parts");
     GD_REQUIRE(nstreams >= 0 && (nstreams == 0 || producer_streams), "gd_upload_device: bad producer stream list");
-    const int sz = dtype_bytes(dtype);
+    const int sz = gd_dtype_bytes(dtype);
     GD_REQUIRE(sz != 0, "gd_upload_device: unknown sample element type");
     GD_HIP(hipSetDevice(ctx->device));
     const int64_t ncols = parts[0].cols;
@@ -358,7 +363,7 @@ int gd_upload_device(gd_ctx* ctx, const gd_dev_part* parts, int32_t nparts, int3
     }
     GD_REQUIRE(N > 0, "gd_upload_device: no rows");
     GD_REQUIRE(ncols < (1 << 30), "gd_upload_device: too many columns");
-    const int wsz = dtype_bytes(w_dtype);
+    const int wsz = gd_dtype_bytes(w_dtype);
     GD_REQUIRE(!weighted || wsz != 0, "gd_upload_device: unknown weight element type");
     std::vector<int32_t> kept;
     if (keep) {
@@ -374,8 +379,8 @@ int gd_upload_device(gd_ctx* ctx, const gd_dev_part* parts, int32_t nparts, int3
         const gd_dev_part& p = parts[k];
         if (p.rows == 0) continue;
         GD_REQUIRE(!weighted || p.weights, "gd_upload_device: weights given for some parts only");
-        GD_TRY(check_array(ctx, "gd_upload_device samples", p.base, p.rows, p.cols, p.row_stride, p.col_stride, sz));
-        if (weighted) GD_TRY(check_array(ctx, "gd_upload_device weights", p.weights, p.rows, 1, p.w_stride, 0, wsz));
+        GD_TRY(gd_check_device_array(ctx, "gd_upload_device samples", p.base, p.rows, p.cols, p.row_stride, p.col_stride, sz));
+        if (weighted) GD_TRY(gd_check_device_array(ctx, "gd_upload_device weights", p.weights, p.rows, 1, p.w_stride, 0, wsz));
     }
     // validated: from here on the previous sample set is gone
     GD_TRY(gd_upload_release(ctx));
@@ -400,12 +405,12 @@ int gd_upload_device(gd_ctx* ctx, const gd_dev_part* parts, int32_t nparts, int3
 int gd_fetch_device_array(gd_ctx* ctx, const void* base, int64_t rows, int64_t cols, int64_t row_stride, int64_t col_stride,
                           int32_t dtype, void* producer_stream, double* out) {
     if (!ctx) return GD_ERR_BADARG;
-    const int sz = dtype_bytes(dtype);
+    const int sz = gd_dtype_bytes(dtype);
     GD_REQUIRE(sz != 0, "gd_fetch_device_array: unknown element type");
     GD_REQUIRE(out, "gd_fetch_device_array: null destination");
     GD_HIP(hipSetDevice(ctx->device));
-    GD_TRY(check_array(ctx, "gd_fetch_device_array", base, rows, cols, row_stride, col_stride, sz));
-    GD_TRY(wait_producer(ctx, producer_stream));
+    GD_TRY(gd_check_device_array(ctx, "gd_fetch_device_array", base, rows, cols, row_stride, col_stride, sz));
+    GD_TRY(gd_wait_for_stream(ctx, producer_stream));
     const int64_t per = std::max<int64_t>(1, ((int64_t)32 << 20) / (cols * 8));  // rows per staged block
     for (int64_t r0 = 0; r0 < rows; r0 += per) {
         const int64_t nr = std::min(per, rows - r0);

@@ -2,8 +2,7 @@
 // thin, removeBurn, deleteFixedParams, addDerived, re-weighting) without the host's fancy indexing and the re-upload.
 //
 // gd_select_samples builds the new set beside the old one:
-//   row list   a mask or a weight threshold becomes an ascending int32 row list: the ordered compaction of tilescan.hpp
-//              over tiles of GD_SEL_TILE rows with SelKeep as its predicate (count, scan to offsets and the total K, place).
+//   row list   a mask or a weight threshold becomes an ascending int32 row list (rowlist.hpp).
 //   gather     k_sel_gather: out[c][k] = in[col(c)][rows[k]].  A thread owns two consecutive k (one 16-byte store per
 //              column), keeps its two row numbers in registers and walks a chunk of GATHER_CH columns with all the chunk's
 //              loads in flight before the first store; grid (row tiles, column chunks).  For an ascending list the loads of
@@ -17,33 +16,11 @@
 #include <vector>
 
 #include "ctx.hpp"
-#include "tilescan.hpp"
+#include "rowlist.hpp"
 
 namespace {
 
-constexpr int kSelThreads = 256;
-constexpr int kSelIters = GD_SEL_TILE / kSelThreads;  // rounds of a block over its tile
-constexpr int GATHER_CH = 8;                          // columns per block of the gather
-static_assert(GD_SEL_TILE % kSelThreads == 0, "a tile is a whole number of block rounds");
-
-// the predicate of the compaction (tilescan.hpp): row i is kept when its mask byte is set (mask != nullptr), else when its
-// weight exceeds thr
-struct SelKeep {
-    const unsigned char* mask;
-    const double* w;
-    double thr;
-    int64_t N;
-
-    __device__ __forceinline__ unsigned operator()(int64_t tile) const {
-        unsigned m = 0;
-#pragma unroll
-        for (int q = 0; q < kSelIters; ++q) {
-            const int64_t i = tile * GD_SEL_TILE + q * kSelThreads + threadIdx.x;
-            if (i < N && (mask ? mask[i] != 0 : w[i] > thr)) m |= 1u << q;
-        }
-        return m;
-    }
-};
+constexpr int GATHER_CH = 8;  // columns per block of the gather
 
 // out[c * ld_out + k] = in[col(c) * ld_in + rows[k]], col(c) = colmap[c] (colmap == nullptr: c), k < K, c < ncols.
 // out + c * ld_out is 16-byte aligned for every c (ld_out is a multiple of 512, the base a hipMalloc block).
@@ -94,17 +71,6 @@ struct Plan {
     bool contiguous = false;      // ALL / RANGE
     int64_t lo = 0, K = 0;        // K: known for ALL / RANGE / ROWS_I32, else found by the scan
 };
-
-// the device row list of a mask / threshold selection, in scratch2 from `d_rows` on; K comes back
-int build_row_list(gd_ctx* ctx, const unsigned char* d_mask, double thr, long long* d_cnt, int nb, int32_t* d_rows, int64_t* K_out) {
-    const SelKeep keep = {d_mask, ctx->w, thr, ctx->N};
-    long long total = 0;
-    GD_TRY((gd_compact_count<kSelThreads, kSelIters>(ctx, keep, nb, d_cnt, &total)));
-    GD_TRY((gd_compact_place<kSelThreads, kSelIters>(ctx, keep, nb, d_cnt, d_rows, ctx->N)));  // the list holds N entries
-    GD_TRY(gd_stream_sync(ctx));
-    *K_out = total;
-    return GD_OK;
-}
 
 // fills the new allocations (cols / w / w8 are the caller's locals: it frees them when this fails)
 int select_build(gd_ctx* ctx, const gd_selection* sel, const Plan& p, const int32_t* d_rows, const int32_t* d_colmap,
@@ -177,13 +143,7 @@ int gd_select_samples(gd_ctx* ctx, const gd_selection* sel, int64_t* count_out) 
             GD_REQUIRE(sel->K > 0, "gd_select_samples: no rows selected");
             GD_REQUIRE(sel->rows, "gd_select_samples: null row list");
             p.K = sel->K;
-            if (!on_device) {
-                const int32_t* r = (const int32_t*)sel->rows;
-                for (int64_t k = 0; k < sel->K; ++k)
-                    if (r[k] < 0 || r[k] >= N)
-                        return gd_fail(ctx, GD_ERR_BADARG, "gd_select_samples: row %d (entry %lld of the list) is outside [0, %lld)", (int)r[k],
-                                       (long long)k, (long long)N);
-            }
+            if (!on_device) GD_TRY(check_host_row_list(ctx, "gd_select_samples", (const int32_t*)sel->rows, sel->K, N));
             break;
         default:
             return gd_fail(ctx, GD_ERR_BADARG, "gd_select_samples: unknown row selection %d", (int)sel->row_kind);
@@ -254,7 +214,7 @@ int gd_select_samples(gd_ctx* ctx, const gd_selection* sel, int64_t* count_out) 
                     d_mask = b_mask;
                 }
             }
-            GD_TRY(build_row_list(ctx, d_mask, sel->thr, b_cnt, nb, b_rows, &K));
+            GD_TRY(build_row_list(ctx, d_mask, ctx->w, sel->thr, b_cnt, nb, b_rows, &K));
             d_rows = b_rows;
             GD_REQUIRE(K > 0, "gd_select_samples: no rows selected");
             GD_REQUIRE(sel->weight_kind != GD_SEL_W_REPLACE || sel->K == K,

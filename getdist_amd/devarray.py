@@ -1,10 +1,16 @@
 """
-Device arrays as input: what MCSamples needs to know about a ``torch.Tensor`` on the GPU or any object with
-``__cuda_array_interface__`` (CuPy, numba) to hand it to gd_upload_device -- pointer, shape, strides in elements, element
-type, device and producer stream.  Nothing here imports torch or CuPy: the objects are recognised by their attributes.
+Device arrays as input and as output.
 
-Out of scope: handing the resident columns OUT as device arrays (their lifetime across re-uploads needs a design of its
-own), device row compaction, integer element types.
+In: what MCSamples needs to know about a ``torch.Tensor`` on the GPU or any object with ``__cuda_array_interface__`` (CuPy,
+numba) to hand it to gd_upload_device -- pointer, shape, strides in elements, element type, device and producer stream.
+
+Out: :class:`DeviceArray`, the owning result of ``getDeviceSamples`` / ``getDeviceWeights`` (gd_export_device).  An export is
+a SNAPSHOT, never an alias of the resident columns: the values are copied device to device into memory the sample set does
+not own, so every mutator and re-upload stays free to replace the resident set, and the array stays valid after the sample
+set and its context are gone.
+
+Nothing here imports torch or CuPy: the objects are recognised by their attributes.  Out of scope: integer element types,
+DLPack capsules, zero-copy views of the resident columns.
 """
 
 import ctypes
@@ -144,11 +150,92 @@ def _describe_interface(obj, cai):
     return DevArray(cai["data"][0] or 0, shape, strides, code, None, stream, obj)
 
 
+DTYPE_NAMES = {"float64": GD_DT_F64, "float32": GD_DT_F32, "float16": GD_DT_F16, "bfloat16": GD_DT_BF16}
+_TYPESTR = {GD_DT_F64: "<f8", GD_DT_F32: "<f4", GD_DT_F16: "<f2", GD_DT_BF16: "<i2"}  # (the interface has no bfloat16)
+
+
+def dtype_code(dtype):
+    """The GD_DT_* code of ``dtype``: a numpy float type (or its name), a torch dtype, or "bfloat16" """
+    name = dtype if isinstance(dtype, str) else str(dtype)
+    if name in _TORCH_TYPES:
+        return _TORCH_TYPES[name]
+    if name not in DTYPE_NAMES:
+        try:
+            name = np.dtype(dtype).name
+        except TypeError:
+            pass
+    if name not in DTYPE_NAMES:
+        raise ValueError("dtype must be float64, float32, float16 or \"bfloat16\", not %r" % (dtype,))
+    return DTYPE_NAMES[name]
+
+
+class DeviceArray:
+    """A 1-D or 2-D array in device memory that owns its block (``block``: anything with ``ptr``, ``device`` and
+    ``fetch(host_array)``, which frees the memory when its last reference goes: _lib.ExportBlock).  ``strides`` are in
+    elements; ``dtype`` is a numpy dtype, for bfloat16 the string "bfloat16".  ``stream`` is what the interface dictionary
+    announces: None for an array that was complete before it was returned."""
+
+    def __init__(self, block, shape, strides, code, stream=None):
+        self.block, self.shape, self.strides = block, tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+        self.code, self.stream = code, stream
+
+    @classmethod
+    def allocate(cls, ctx, shape, code, order="C"):
+        """A new array of ``shape`` in C or Fortran order, in memory from ``ctx.export_block`` (owned by the array alone)"""
+        shape = tuple(int(v) for v in shape)
+        if order not in ("C", "F"):
+            raise ValueError("order must be 'C' or 'F'")
+        strides, run = [], 1
+        for extent in (reversed(shape) if order == "C" else shape):
+            strides.append(run)
+            run *= max(extent, 1)
+        strides = tuple(reversed(strides)) if order == "C" else tuple(strides)
+        size = int(np.prod(shape)) if shape else 1
+        return cls(ctx.export_block(size * ITEMSIZE[code]), shape, strides, code)
+
+    ptr = property(lambda self: self.block.ptr)
+    device = property(lambda self: self.block.device)
+    ndim = property(lambda self: len(self.shape))
+    size = property(lambda self: int(np.prod(self.shape)) if self.shape else 1)
+    itemsize = property(lambda self: ITEMSIZE[self.code])
+    nbytes = property(lambda self: self.size * self.itemsize)
+    dtype = property(lambda self: np.dtype(_NUMPY_TYPE[self.code]) if self.code in _NUMPY_TYPE else "bfloat16")
+
+    @property
+    def __cuda_array_interface__(self):
+        return dict(shape=self.shape, typestr=_TYPESTR[self.code], data=(self.ptr if self.size else 0, False), version=3,
+                    strides=tuple(s * self.itemsize for s in self.strides), stream=self.stream)
+
+    def describe(self):
+        """the DevArray of this array (it keeps the array, and so the memory, alive)"""
+        return DevArray(self.ptr, self.shape, self.strides, self.code, self.device, self.stream, self)
+
+    def numpy(self):
+        """A host copy in the array's shape and order; bfloat16 comes back as its uint16 bit patterns."""
+        dt = _NUMPY_TYPE.get(self.code, np.uint16)
+        flat = np.empty(self.size, dtype=dt)
+        if self.size:
+            self.block.fetch(flat)
+        fortran = self.ndim == 2 and self.strides[0] == 1 and self.shape[1] > 1
+        return flat.reshape(self.shape[::-1]).T if fortran else flat.reshape(self.shape)
+
+    def torch(self):
+        """The same memory as a torch tensor (no copy; the tensor keeps this array alive).  torch is not imported here: the
+        ``torch`` the process has already imported is used."""
+        torch = sys.modules.get("torch")
+        if torch is None:
+            raise RuntimeError("DeviceArray.torch(): import torch first (before the first sample set is made)")
+        t = torch.as_tensor(self, device="cuda:%d" % self.device)
+        return t.view(torch.bfloat16) if self.code == GD_DT_BF16 else t
+
+
 def describe(obj):
     """The DevArray of a device array, None for anything that is not one (numpy arrays, lists, CPU tensors: those go on
     through np.asarray).  TypeError for a device array of an element type that is not served (integers, complex)."""
     if isinstance(obj, DevArray):
         return obj
+    if isinstance(obj, DeviceArray):
+        return obj.describe()
     if isinstance(obj, (np.ndarray, list, tuple, str, bytes, int, float)) or obj is None:
         return None
     is_cuda = getattr(obj, "is_cuda", None)

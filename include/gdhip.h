@@ -84,7 +84,8 @@ int gd_timer_stop_ms(gd_ctx* ctx, double* ms_out);
 int gd_upload(gd_ctx* ctx, const double* X, int64_t N, int64_t n, int64_t row_stride, int64_t col_stride,
               const double* weights);
 int gd_num_rows(gd_ctx* ctx, int64_t* N, int64_t* n);
-/* device pointer to column j (N doubles) / weights (NULL if unit) -- for tests and zero-copy users */
+/* device pointer to column j (N doubles) / weights (NULL if unit) -- for tests and zero-copy users; an ALIAS of the resident
+ * set that dies with the next upload or mutator (gd_export_device hands out copies that do not) */
 int gd_column_ptr(gd_ctx* ctx, int64_t j, void** d_out);
 /* gd_clone_samples: the device half of MCSamples.copy (mcsamples.py:308-322, copy.deepcopy of a sample set): dst receives
  *   allocations of its OWN holding src's N x n columns and sample weights (none for a unit-weight set), filled by
@@ -199,6 +200,65 @@ typedef struct gd_selection {
 } gd_selection;
 int gd_select_samples(gd_ctx* ctx, const gd_selection* sel, int64_t* count_out);
 int gd_set_weights(gd_ctx* ctx, const double* w_host);
+
+/* ---------------------------------------------------------------- the resident samples as device arrays
+ * gd_export_device: the mirror image of gd_upload_device.  Selected rows of selected resident columns (or of the sample
+ *   weights) are written into a DEVICE array of the caller's, in the element type and with the strides it states.  The
+ *   result is a SNAPSHOT, a copy device to device into memory the sample set does not own: every mutator and re-upload may
+ *   replace the resident set afterwards.  The call only reads the set, so a borrowed one (gd_attach_samples) may be exported.
+ *   Rows: row_kind, flags, lo, hi, rows, K, thr exactly as in gd_selection (GD_SEL_ALL / RANGE / MASK_U8 / WEIGHT_GT /
+ *     ROWS_I32, GD_SEL_ROWS_ON_DEVICE; masks and thresholds become an ascending row list by the same compaction; a host list
+ *     is checked against [0, N), a device list is trusted; a list may be in any order, with repeats), and one kind more:
+ *     GD_EXP_ROWS_COLUMN_NZ, the rows whose value in resident column mask_col (a spare column, where
+ *     gd_expr_eval(..., GD_EX_TO_COLUMN, slot) leaves a boolean expression as 0.0 / 1.0) is != 0: the mask never leaves the
+ *     device.  Unlike gd_select_samples a selection may be EMPTY (lo == hi, K == 0, nothing kept).
+ *   Columns: cols[m] are resident column indices in any order, repeats allowed, the spare columns n .. n + 3 included,
+ *     1 <= m <= 65535.  cols == NULL: the sample weight column (m is ignored and taken as 1); a unit-weight set writes 1.
+ *   Destination: element (k, c) of the result -- k-th selected row, c-th listed column -- goes to
+ *     base[k * row_stride + c * col_stride] (strides in ELEMENTS of `dtype`, >= 0), converted from fp64 with IEEE
+ *     round-to-nearest-even in ONE step (csrc/cvtfloat.hpp; overflow gives inf, subnormal results are kept).  Only these
+ *     elements are written: nothing between or behind them.  rows_capacity is the number of rows the destination has room for.
+ *   consumer_stream: the caller's stream that used the destination last and will use it next: NULL none, (void*)1 the legacy
+ *     default stream, (void*)2 the per-thread default stream, else a hipStream_t.  The library's stream waits (an event) for
+ *     the work that stream has been given before the first store, and that stream waits (an event) for the export's kernels;
+ *     the host waits for neither.  With NULL the call returns once the destination is written.
+ *   *count_out (required) receives K, the number of rows selected.  K > rows_capacity: nothing is written and the call
+ *     returns GD_DRAW_MORE_ROWS -- a first call with rows_capacity 0 (base is then not looked at) is how a caller learns K for
+ *     a mask before it allocates.  K == 0 launches nothing and returns GD_OK.
+ *   Kernels, one per call, chosen from the strides and the alignment as on the way in: slab (contiguous rows into a
+ *     row-major destination, col_stride 1: a block takes R rows, reads each column's run with 16-byte loads into LDS and
+ *     writes converted rows, 16-byte stores when row_stride == m), column (row_stride 1 or a single column: a converting
+ *     copy, two rows per lane), tile (any other strides: 32 x 32), gathered (any row list).
+ *   Every check passes BEFORE anything is launched; a refusal writes nothing.  With rows_capacity > 0 the destination must
+ *     be what gd_upload_device accepts as a source, with the same statuses (GD_ERR_DECLINED for page-locked / managed memory
+ *     and negative strides, GD_ERR_OTHER_DEVICE, GD_ERR_NOT_DEVICE, GD_ERR_BADARG for a misaligned pointer or a span that
+ *     leaves its allocation), and GD_ERR_BADARG when two of its rows_capacity x m elements share an address (a zero stride
+ *     with extent > 1, row_stride < m with col_stride 1).  GD_ERR_BADARG also: no resident set, N >= 2^31 with a row list,
+ *     a range outside [0, N] or lo > hi, a missing pointer, an unknown kind or dtype, a column out of range, m outside
+ *     1 .. 65535, a host row number outside [0, N), negative rows_capacity.
+ * gd_export_alloc / gd_export_free / gd_export_fetch: device memory for a result that must outlive every context
+ *   (devarray.DeviceArray): allocated on `device` with no context, so that it neither comes from nor returns to a context's
+ *   block cache and stays valid across mutators, re-uploads and gd_destroy; freed, and read back to the host, with the
+ *   device index alone.  They return GD_OK, GD_ERR_NOMEM or GD_ERR_HIP (no context: no error text). */
+#define GD_EXP_ROWS_COLUMN_NZ 5
+typedef struct gd_export {
+    int32_t row_kind, flags; /* a GD_SEL_* row kind or GD_EXP_ROWS_COLUMN_NZ; GD_SEL_ROWS_ON_DEVICE */
+    int64_t lo, hi;          /* GD_SEL_RANGE */
+    const void* rows;        /* GD_SEL_MASK_U8: N bytes; GD_SEL_ROWS_I32: K int32 */
+    int64_t K;               /* GD_SEL_ROWS_I32: the list's length */
+    double thr;              /* GD_SEL_WEIGHT_GT */
+    int32_t mask_col;        /* GD_EXP_ROWS_COLUMN_NZ */
+    int32_t m;
+    const int32_t* cols;     /* NULL: the sample weights */
+    void* base;
+    int64_t rows_capacity, row_stride, col_stride;
+    int32_t dtype, reserved; /* GD_DT_* */
+    void* consumer_stream;
+} gd_export;
+int gd_export_device(gd_ctx* ctx, const gd_export* ex, int64_t* count_out);
+int gd_export_alloc(int32_t device, int64_t bytes, void** d_out);
+int gd_export_free(int32_t device, void* d_ptr);
+int gd_export_fetch(int32_t device, void* dst, const void* d_src, int64_t bytes);
 
 /* ---------------------------------------------------------------- weighted moments -------------
  * gd_weight_stats: norm=sum w (chains.py:312), max w (chains.py:1349), sum w^2 (chains.py:499,536),
