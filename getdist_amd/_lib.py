@@ -147,6 +147,8 @@ SIGNATURES = {
     "gd_batch2d_finish": (C.c_int, [_p]),
     "gd_batch2d_invalidate": (C.c_int, [_p]),
     "gd_batch2d_exchanges": (C.c_int, [_p, C.POINTER(C.c_int64)]),
+    "gd_prepare_params": (C.c_int, [_p, _p, _p, _pi32, _i32, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pd, C.POINTER(C.c_int32), _p]),
+    "gd_prepare_ahead_counts": (C.c_int, [_p, C.POINTER(C.c_int64)]),
     "gd_comm_rccl_path": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     "gd_upload_shard": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
     "gd_comm_share_columns": (C.c_int, [_p, C.POINTER(C.c_int64)]),
@@ -288,6 +290,18 @@ def load_library():
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+class PrepareSettings(C.Structure):
+    """gd_prepare_settings"""
+
+    _fields_ = [("fine_bins_2D", C.c_int32), ("auto_bandwidth", C.c_int32), ("uncorrelated_sampler", C.c_int32),
+                ("ahead", C.c_int32)]
+
+
+# gd_prepared_param
+PREPARED_PARAM = np.dtype([("range_min", np.float64), ("range_max", np.float64), ("sigma_range", np.float64),
+                           ("has_limits_bot", np.int32), ("has_limits_top", np.int32)])
 
 
 def _dp(a):
@@ -919,6 +933,35 @@ class Context:
         self._check(self.lib.gd_quantiles_mm_probe(self.h, _ip(cols), len(cols), 0, self.N, _dp(targets), targets.shape[1], _dp(mm),
                                                    _dp(out), _dp(means), _dp(probe), C.byref(done)))
         return out, (probe if done.value else None)
+
+    def prepare_params(self, cols, targets, minmax, means, variances, err, limits, has_bot, has_top, twin=None, fine_bins_2D=0,
+                       auto_bandwidth=False, uncorrelated_sampler=False, ahead=0):
+        """gd_prepare_params over whole columns: (quantiles, lag probe or None, records).  ``records`` holds a row
+        (range_min, range_max, sigma_range, has_limits_bot, has_limits_top) per column, the scalar tail of _initParam worked
+        out by the library; ``ahead`` (bit 0: N_eff lag sums, bit 1: index columns) lets it enqueue, without waiting, what the
+        next batched 2D call over these columns starts with."""
+        cols = _i32arr(cols)
+        m = len(cols)
+        targets = _f64arr(targets).reshape(m, 11)
+        mm = _f64arr(minmax).reshape(m, 2)
+        means, variances, err = _f64arr(means), _f64arr(variances), _f64arr(err)
+        limits = _f64arr(limits).reshape(m, 2)
+        out, probe = np.zeros_like(targets), np.zeros((m, 8))
+        recs = np.zeros(m, dtype=PREPARED_PARAM)
+        recs["has_limits_bot"], recs["has_limits_top"] = has_bot, has_top
+        settings = PrepareSettings(int(fine_bins_2D), int(bool(auto_bandwidth)), int(bool(uncorrelated_sampler)), int(ahead))
+        done = C.c_int32(0)
+        self._check(self.lib.gd_prepare_params(self.h, None if twin is None else twin.h, C.byref(settings), _ip(cols), m, _dp(targets),
+                                               _dp(mm), _dp(means), _dp(variances), _dp(err), _dp(limits), _dp(out), _dp(probe),
+                                               C.byref(done), recs.ctypes.data))
+        return out, (probe if done.value else None), recs
+
+    def prepare_ahead_counts(self):
+        """(enqueued, consumed, discarded): pieces gd_prepare_params has enqueued ahead on this context, how many a batched
+        call used, how many were waited for and dropped."""
+        out = np.zeros(3, dtype=np.int64)
+        self._check(self.lib.gd_prepare_ahead_counts(self.h, out.ctypes.data_as(_pi64)))
+        return tuple(int(v) for v in out)
 
     def autocov_lags(self, col, mean, k0, nlags):
         out = np.zeros(nlags)

@@ -187,6 +187,50 @@ static inline void bin_edges(const gd_param2d& p, double* binmin, double* binmax
     *binmin = lo, *binmax = hi;
 }
 
+// The scalar tail of _initParam (mcsamples.py:1440-1484) for one parameter, given what the quantile select and the base
+// statistics delivered: q = {range_confidence quantile, its mirror, the deciles 0.1 .. 0.9}.  The same fp64 operations in
+// the order MCSamples._init_params performs them (np.min over the spans of four, Python's min(err, scale)).
+// `rec` arrives with has_limits_bot / has_limits_top as the prior ranges set them (_initLimits) and leaves with
+// range_min, range_max, sigma_range and the limit flags final.
+static inline void prepare_tail(const double q[11], double col_min, double col_max, double err, double limmin, double limmax,
+                                gd_prepared_param* rec) {
+    double confids[11];
+    confids[0] = col_min;
+    for (int k = 0; k < 9; ++k) confids[1 + k] = q[2 + k];
+    confids[10] = col_max;
+    double diffs[7];
+    for (int k = 0; k < 7; ++k) diffs[k] = confids[k + 4] - confids[k];
+    double mn = diffs[0];
+    for (int k = 1; k < 7; ++k) mn = np_minimum(mn, diffs[k]);
+    const double scale = mn / 1.049;
+    bool flat = true;
+    const double lo = err * 1.049, hi = scale * 1.5;
+    for (int k = 0; k < 7; ++k) flat = flat && (diffs[k] > lo) && (diffs[k] < hi);
+    rec->sigma_range = flat ? scale : (scale < err ? scale : err);  // min(par.err, scale)
+    double range_min = q[0], range_max = q[1];
+    const double smooth_1D = rec->sigma_range * 0.4;
+    if (rec->has_limits_bot) {
+        if (range_min - limmin > 2 * smooth_1D && col_min - limmin > smooth_1D)
+            rec->has_limits_bot = 0;  // long way from limit
+        else
+            range_min = limmin;
+    }
+    if (rec->has_limits_top) {
+        if (limmax - range_max > 2 * smooth_1D && limmax - col_max > smooth_1D)
+            rec->has_limits_top = 0;
+        else
+            range_max = limmax;
+    }
+    if (!rec->has_limits_bot) range_min -= smooth_1D * 2;
+    if (!rec->has_limits_top) range_max += smooth_1D * 2;
+    rec->range_min = range_min, rec->range_max = range_max;
+}
+
+// Thresholds the batched call and the preparation entry (gd_prepare_params, which enqueues ahead what the call starts with)
+// both read: the fewest pairs of the base grid's class that take the byte-index route, and min_corr of the N_eff estimate.
+static constexpr int kByteIndexMinPairs = 64;
+static constexpr double kNeffMinCorr = 0.05;
+
 // ---- effective sample numbers (chains.py:477-574 via mcsamples.py:1230-1235) -------------------------------------------
 struct NeffInput {
     int64_t N;
@@ -250,6 +294,54 @@ static inline int neff_from_lags(const NeffInput& in, int64_t maxoff, double min
     if (rc) return rc;
     *neff_out = py_pow(in.norm, 2.0) / Nn;
     return 0;
+}
+
+// The first launch of the N_eff lag sums for m columns, from their autocovariance probe (lag0: m x nl sums at lags
+// 0 .. nl - 1, nl = min(8, N / 10 + 1)): the kernel width and the largest offset per column, the lag list of the launch.
+// Returns -1, or the row of the first column whose correlation outlasts the probe (getCorrelationLength's long route).
+struct LagPlan {
+    std::vector<double> inv4s2;
+    std::vector<int64_t> maxoffs, lags;
+    int ntail = 0;  // 1: lag 1 rides behind the five lags from N / 2; 2: lag 2 as well
+};
+static inline int lag_plan(int64_t N, int m, int nl, const double* lag0, const double* var, const double* sigma_range,
+                           const double* err, double min_corr, LagPlan& lp) {
+    const int64_t max_off = N / 10;
+    lp.inv4s2.assign(m, NAN), lp.maxoffs.assign(m, 0), lp.lags.clear(), lp.ntail = 0;
+    bool all_uncorrelated_at_lag_1 = true;  // by the probe: then the speculative corr_k(2) is left out of the launch
+    for (int row = 0; row < m; ++row) {
+        double c[8];
+        for (int k = 0; k < nl; ++k) c[k] = lag0[(size_t)row * nl + k] / (double)(N - k) / var[row];
+        int first_below = -1;
+        for (int k = 0; k < nl; ++k)
+            if (!(c[k] > min_corr * c[0])) {
+                first_below = k;
+                break;
+            }
+        if (first_below != 1) all_uncorrelated_at_lag_1 = false;
+        double corrlen;
+        if (first_below >= 0) {
+            double sum = 0.0;
+            for (int k = 1; k < first_below; ++k) sum += c[k];
+            corrlen = c[0] + 2 * sum;
+        } else if (nl == max_off + 1) {
+            corrlen = c[0];
+        } else {
+            return row;
+        }
+        const double sr = sigma_range[row];
+        const double kstd = ((isnan(sr) || sr == 0.0) ? err[row] : sr) * 0.2;  // (par.sigma_range or self.sddev[j]) * 0.2
+        lp.inv4s2[row] = 1.0 / (4 * py_pow(kstd, 2.0));
+        lp.maxoffs[row] = (int64_t)(corrlen * 1.5) + 4;
+    }
+    const int64_t uncorr_len = N / 2;
+    for (int64_t k = uncorr_len; k < uncorr_len + 5; ++k) lp.lags.push_back(k);
+    // corr_k(1) always; corr_k(2) -- needed only by a chain still correlated at lag 1 (chains.py:541-545) -- rides along
+    // unless the probe shows every column below the threshold at lag 1 already: six exponentials per sample instead of
+    // seven (the launch is bound by them); a column the probe misjudged fetches its lag 2 by itself (neff_from_lags)
+    for (int64_t k : {1, 2})
+        if (k <= N / 10 && (k == 1 || !all_uncorrelated_at_lag_1)) lp.lags.push_back(k), ++lp.ntail;
+    return -1;
 }
 
 // ---- the bandwidth plan (mcsamples.py:1325-1409) ----------------------------------------------------------------------
@@ -336,6 +428,10 @@ struct State {
     Pending prev;                                        // the last lazily delivered call
     void* aux = nullptr;                                 // third context (stream) of large calls: shear chain, get_h
     void* aux2 = nullptr;                                // fourth: the DEFERRED shear chain + up-scaled classes (round 6)
+    // work the preparation entry (gd_prepare_params) enqueued ahead of the next batched call: the binding's own record
+    // (batch2d.hip), and whether N_eff lag sums are among it (neff_batch then has nothing to hold back)
+    void* ahead = nullptr;
+    std::atomic<bool> neff_ahead{false};
     int64_t exchanges_entered = 0;                       // N_eff collectives the library ENTERED over the communicator (whether or
                                                          // not the call went on to succeed): gd_batch2d_exchanges
     static constexpr int64_t kCacheLimit = 16LL << 30;
@@ -663,7 +759,7 @@ struct Call {
     double* M(int k) { return meta + (size_t)k * GD_BATCH2D_META; }
 
     // -- N_eff of the listed columns that have none yet (the batched form of _get1DNeff, mcsamples.py:1230-1235)
-    int neff_batch(const std::vector<int>& js, bool owned_only, double min_corr = 0.05) {
+    int neff_batch(const std::vector<int>& js, bool owned_only, double min_corr = kNeffMinCorr) {
         std::vector<int32_t> todo;
         for (int j : js)
             if (isnan(par[j].neff) && (!owned_only || (par[j].owned & 1))) todo.push_back(j);
@@ -689,51 +785,30 @@ struct Call {
             for (int row = 0; row < m; ++row) means[row] = par[todo[row]].mean;
             GDB_DEV(h, ops.autocov_lags_batch(h, todo.data(), m, means.data(), 0, nl, lag0.data()));
         }
-        std::vector<double> kstd(m), inv4s2(m);
-        std::vector<int64_t> maxoffs(m);
-        bool all_uncorrelated_at_lag_1 = true;  // by the probe: then the speculative corr_k(2) is left out of the launch
-        for (int row = 0; row < m; ++row) {
-            const gd_param2d& p = par[todo[row]];
-            double c[8];
-            for (int k = 0; k < nl; ++k) c[k] = lag0[(size_t)row * nl + k] / (double)(N - k) / p.var;
-            int first_below = -1;
-            for (int k = 0; k < nl; ++k)
-                if (!(c[k] > min_corr * c[0])) {
-                    first_below = k;
-                    break;
-                }
-            if (first_below != 1) all_uncorrelated_at_lag_1 = false;
-            double corrlen;
-            if (first_below >= 0) {
-                double sum = 0.0;
-                for (int k = 1; k < first_below; ++k) sum += c[k];
-                corrlen = c[0] + 2 * sum;
-            } else if (nl == max_off + 1) {
-                corrlen = c[0];
-            } else {
+        LagPlan lp;
+        {
+            std::vector<double> var(m), sr(m), er(m);
+            for (int row = 0; row < m; ++row) {
+                const gd_param2d& p = par[todo[row]];
+                var[row] = p.var, sr[row] = p.sigma_range, er[row] = p.err;
+            }
+            const int long_row = lag_plan(N, m, nl, lag0.data(), var.data(), sr.data(), er.data(), min_corr, lp);
+            if (long_row >= 0) {
                 char buf[160];
                 snprintf(buf, sizeof buf, "column %d: the chain's correlation outlasts the 8-lag probe (getCorrelationLength's long route)",
-                         (int)todo[row]);
+                         (int)todo[long_row]);
                 return fail(GD_BATCH2D_NEED_NEFF, buf);
             }
-            const double sr = p.sigma_range;
-            kstd[row] = ((isnan(sr) || sr == 0.0) ? p.err : sr) * 0.2;  // (par.sigma_range or self.sddev[j]) * 0.2
-            inv4s2[row] = 1.0 / (4 * py_pow(kstd[row], 2.0));
-            maxoffs[row] = (int64_t)(corrlen * 1.5) + 4;
         }
-        std::vector<int64_t> lags;
-        const int64_t uncorr_len = N / 2;
-        for (int64_t k = uncorr_len; k < uncorr_len + 5; ++k) lags.push_back(k);
-        // corr_k(1) always; corr_k(2) -- needed only by a chain still correlated at lag 1 (chains.py:541-545) -- rides along
-        // unless the probe shows every column below the threshold at lag 1 already: six exponentials per sample instead of
-        // seven (the launch is bound by them); a column the probe misjudged fetches its lag 2 by itself (neff_from_lags)
-        int ntail = 0;
-        for (int64_t k : {1, 2})
-            if (k <= N / 10 && (k == 1 || !all_uncorrelated_at_lag_1)) lags.push_back(k), ++ntail;
+        const std::vector<double>& inv4s2 = lp.inv4s2;
+        const std::vector<int64_t>&maxoffs = lp.maxoffs, &lags = lp.lags;
+        const int ntail = lp.ntail;
         const int L = (int)lags.size();
         std::vector<double> sums((size_t)m * L);
         mark("neff: probe done");
-        if (hold_neff_for_binning) {
+        // (lag sums the preparation entry has already enqueued for this sample set: nothing to hold back, the binding of
+        // kde_lag_sums_batch hands their result over or, on any mismatch, waits for them and launches afresh)
+        if (hold_neff_for_binning && !st.neff_ahead.load()) {
             const auto t0 = std::chrono::steady_clock::now();
             while (!bin_launching.load() && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2)) std::this_thread::yield();
             int hold_us = 120;  // (its launches go out)  GDHIP_BATCH_NEFF_HOLD_US: tuning knob
@@ -863,7 +938,7 @@ struct Call {
             const std::vector<int>& members = classes.at(F);
             const int B = (int)members.size();
             int rc = 0;
-            if (F == 256 && (unit_weights || byte_index_weights) && B >= 64) {
+            if (F == 256 && (unit_weights || byte_index_weights) && B >= kByteIndexMinPairs) {
                 // the base grid of a unit-weight triangle: byte indices, packed 16-bit counters, one block per pair
                 std::vector<int> cols;
                 std::vector<char> seen(n, 0);

@@ -1494,16 +1494,21 @@ int gd_hist2d_prebinned(gd_ctx* ctx, int32_t B, const void* const* d_idx_x, cons
     return rc;
 }
 
-int gd_prebin8_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width, int32_t F,
-                     void* const* d_idx_out, int64_t* bad_out) {
-    GD_REQUIRE(ctx && cols && binmin && width && d_idx_out && bad_out && ncols > 0, "bad argument");
-    GD_REQUIRE(ctx->cols, "no samples uploaded");
-    GD_REQUIRE(F >= 2 && F <= 256, "byte indices need fine_bins_2D <= 256");
-    for (int c = 0; c < ncols; ++c) GD_REQUIRE(cols[c] >= 0 && cols[c] < ctx->n + GD_EXTRA_COLS && d_idx_out[c], "bad column");
-    // columns whose bucket columns are valid (the quantile select has walked them) are binned from those 2 bytes per sample
-    const BucketRoute R = bucket_route(ctx, cols, ncols, binmin, width, d_idx_out);
+// The launches of gd_prebin8_batch on ctx->stream, nothing waited for: columns whose bucket columns are valid (the quantile
+// select has walked them) are binned from those 2 bytes per sample, the others by the fp64 kernel.  One function for the call
+// that waits (gd_prebin8_batch) and the one that does not (gd_prebin8_enqueue).
+struct Prebin8Launch {
+    BucketRoute R;
+    std::vector<int> fp_of;  // per requested column: its slot among the fp64 kernel's columns or -1
+    int nfp = 0;
+    unsigned long long *d_bad = nullptr, *d_bad_bq = nullptr;  // out-of-range counts of the two routes (device scratch)
+};
+static int prebin8_launch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width, int32_t F,
+                          void* const* d_idx_out, Prebin8Launch& PL) {
+    PL.R = bucket_route(ctx, cols, ncols, binmin, width, d_idx_out);
+    const BucketRoute& R = PL.R;
     std::vector<PrebinCol8> hc;
-    std::vector<int> fp_of((size_t)ncols, -1);
+    PL.fp_of.assign((size_t)ncols, -1);
     for (int c = 0; c < ncols; ++c) {
         if (R.slot_of[c] >= 0) continue;
         PrebinCol8 r;
@@ -1511,10 +1516,10 @@ int gd_prebin8_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doub
         r.idx = (unsigned char*)d_idx_out[c];
         r.binmin = binmin[c];
         r.width = width[c];
-        fp_of[c] = (int)hc.size();
+        PL.fp_of[c] = (int)hc.size();
         hc.push_back(r);
     }
-    const int nfp = (int)hc.size();
+    const int nfp = PL.nfp = (int)hc.size();
     BucketRouteLayout L(ctx, R);
     ScratchPlan sp;
     auto d_c = sp.take<PrebinCol8>(nfp);
@@ -1530,14 +1535,42 @@ int gd_prebin8_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doub
         if (nblk < 1) nblk = 1;
         k_prebin8_batch<<<dim3(nblk, nfp), 256, 0, ctx->stream>>>(d_c, ctx->N, F, d_bad);
         GD_KERNEL_CHECK();
+        PL.d_bad = d_bad;
     }
-    unsigned long long* d_bad_bq = nullptr;
-    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, L, F, &d_bad_bq));
-    std::vector<unsigned long long> hb((size_t)nfp), hq(R.recs.size());
-    if (nfp) GD_TRY(gd_fetch(ctx, hb.data(), d_bad, (size_t)nfp * 8));
-    if (!R.recs.empty()) GD_TRY(gd_fetch(ctx, hq.data(), d_bad_bq, hq.size() * 8));
+    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, L, F, &PL.d_bad_bq));
+    return GD_OK;
+}
+
+int gd_prebin8_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width, int32_t F,
+                     void* const* d_idx_out, int64_t* bad_out) {
+    GD_REQUIRE(ctx && cols && binmin && width && d_idx_out && bad_out && ncols > 0, "bad argument");
+    GD_REQUIRE(ctx->cols, "no samples uploaded");
+    GD_REQUIRE(F >= 2 && F <= 256, "byte indices need fine_bins_2D <= 256");
+    for (int c = 0; c < ncols; ++c) GD_REQUIRE(cols[c] >= 0 && cols[c] < ctx->n + GD_EXTRA_COLS && d_idx_out[c], "bad column");
+    Prebin8Launch PL;
+    GD_TRY(prebin8_launch(ctx, cols, ncols, binmin, width, F, d_idx_out, PL));
+    const int nfp = PL.nfp;
+    std::vector<unsigned long long> hb((size_t)nfp), hq(PL.R.recs.size());
+    if (nfp) GD_TRY(gd_fetch(ctx, hb.data(), PL.d_bad, (size_t)nfp * 8));
+    if (!PL.R.recs.empty()) GD_TRY(gd_fetch(ctx, hq.data(), PL.d_bad_bq, hq.size() * 8));
     GD_TRY(gd_stream_sync(ctx));
-    for (int c = 0; c < ncols; ++c) bad_out[c] = (int64_t)(R.slot_of[c] >= 0 ? hq[R.slot_of[c]] : hb[fp_of[c]]);
+    for (int c = 0; c < ncols; ++c) bad_out[c] = (int64_t)(PL.R.slot_of[c] >= 0 ? hq[PL.R.slot_of[c]] : hb[PL.fp_of[c]]);
+    return GD_OK;
+}
+
+// bad_pinned: 2 x ncols words of page-locked memory; column c's count arrives in word PL-slot order, so the caller reads
+// bad_pinned[c] through the map this returns in the second half: bad_pinned[ncols + c] = index of column c's word
+int gd_prebin8_enqueue(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width,
+                       void* const* d_idx_out, unsigned long long* bad_pinned) {
+    GD_REQUIRE(ctx && cols && binmin && width && d_idx_out && bad_pinned && ncols > 0, "bad argument");
+    GD_REQUIRE(ctx->cols && !ctx->w, "index columns are enqueued ahead for unit weights only");
+    for (int c = 0; c < ncols; ++c) GD_REQUIRE(cols[c] >= 0 && cols[c] < ctx->n && d_idx_out[c], "bad column");
+    Prebin8Launch PL;
+    GD_TRY(prebin8_launch(ctx, cols, ncols, binmin, width, 256, d_idx_out, PL));
+    const int nfp = PL.nfp;
+    for (int c = 0; c < ncols; ++c) bad_pinned[ncols + c] = (unsigned long long)(PL.R.slot_of[c] >= 0 ? nfp + PL.R.slot_of[c] : PL.fp_of[c]);
+    if (nfp) GD_TRY(gd_fetch_pinned(ctx, bad_pinned, PL.d_bad, (size_t)nfp * 8));
+    if (!PL.R.recs.empty()) GD_TRY(gd_fetch_pinned(ctx, bad_pinned + nfp, PL.d_bad_bq, PL.R.recs.size() * 8));
     return GD_OK;
 }
 

@@ -158,6 +158,26 @@ int gd_dtype_bytes(int dtype);
 int gd_check_device_array(gd_ctx* ctx, const char* what, const void* base, int64_t rows, int64_t cols, int64_t rs, int64_t cs, int sz);
 int gd_wait_for_stream(gd_ctx* ctx, void* producer);
 
+// Work enqueued ahead of the batched 2D call by gd_prepare_params (batch2d.hip), each the launch half of an entry point
+// that otherwise waits, through the same launch function:
+//   stats.hip: the multi-lag launch of gd_kde_lag_sums_batch on ctx->stream with its tables and partial sums in the caller's
+//   device block (gd_kde_lag_sums_partials doubles and 3 x 256-byte-rounded tables), the partials copied to `pinned` by a
+//   kernel behind it; gd_kde_lag_sums_reduce adds them per (column, lag) in block order, as gd_kde_lag_sums_batch does.
+//   binning.hip: the launches of gd_prebin8_batch at F = 256 on ctx->stream; bad_pinned[c] receives column c's count of samples
+//   outside the grid (a copy kernel behind the launches).
+struct gd_kde_lag_ticket {
+    int32_t ncols, nlags, nblk;
+    int order[8];
+};
+extern "C" {
+int64_t gd_kde_lag_sums_partials(const gd_ctx* ctx, int32_t ncols, int32_t nlags);  // 0: the lags do not fit one launch
+int gd_kde_lag_sums_enqueue(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* inv4s2, const int64_t* lags,
+                            int32_t nlags, void* d_block, double* pinned, gd_kde_lag_ticket* t);
+void gd_kde_lag_sums_reduce(const gd_kde_lag_ticket* t, const double* h, double* out);
+int gd_prebin8_enqueue(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width,
+                       void* const* d_idx_out, unsigned long long* bad_pinned);
+}
+
 int gd_fail(gd_ctx* ctx, int code, const char* fmt, ...);
 void gd_comm_release(gd_ctx* ctx);  // comm.hip
 bool gd_ctx_alive(gd_ctx* ctx);

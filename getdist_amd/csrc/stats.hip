@@ -2349,29 +2349,25 @@ int gd_autocov_lags(gd_ctx* ctx, int32_t col, double mean, int64_t k0, int32_t n
     return gd_autocov_lags_batch(ctx, &col, 1, &mean, k0, nlags, out);
 }
 
-int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* inv4s2, const int64_t* lags,
-                          int32_t nlags, double* out) {
-    GD_REQUIRE(ctx && cols && inv4s2 && lags && out && nlags > 0 && nlags <= 64 && ncols > 0, "bad argument");
-    GD_REQUIRE(ctx->cols, "no samples uploaded");
-    GD_REQUIRE_COLUMNS(cols, ncols);
-    for (int i = 0; i < nlags; ++i) GD_REQUIRE(lags[i] > 0 && lags[i] < ctx->N, "lag out of range");
-    const bool multi = nlags <= KDE_LAG_MAX && getenv("GDHIP_KDE_LAG_SINGLE") == nullptr;
+// The launch shape of the lag sums: all lags of a column in one read (`multi`) while they fit KDE_LAG_MAX
+static int kde_lag_blocks(const gd_ctx* ctx, int32_t ncols, int32_t nlags, bool multi) {
     int per_cu = 8;  // blocks of 256 threads per CU (GDHIP_KDE_LAG_BLOCKS_PER_CU: tuning knob)
     if (const char* e = getenv("GDHIP_KDE_LAG_BLOCKS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
     int nblk = multi ? (per_cu * ctx->cu_count + ncols - 1) / ncols : (8 * ctx->cu_count + ncols * nlags - 1) / (ncols * nlags);
     if (nblk < 8) nblk = 8;
     if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-    ScratchPlan sp;
-    auto part = sp.take<double>((int64_t)ncols * (multi ? KDE_LAG_MAX : nlags) * nblk);
-    auto d_lags = sp.take<int64_t>(nlags);
-    auto d_idx = sp.take<int32_t>(ncols);
-    auto d_c = sp.take<double>(ncols);
-    GD_TRY(sp.get(ctx));
+    return nblk;
+}
+
+// The multi-lag launch on ctx->stream, tables uploaded first: `part` receives ncols x nblk x KDE_LAG_MAX partial sums, and
+// order[l] says which of the caller's lags slot l of a partial holds.  One function for the call that waits
+// (gd_kde_lag_sums_batch) and the one that does not (gd_kde_lag_sums_enqueue).
+static int kde_lag_multi_launch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* inv4s2, const int64_t* lags,
+                                int32_t nlags, int nblk, double* part, int64_t* d_lags, int32_t* d_idx, double* d_c, int* order) {
     // the N_eff lag set (five lags from N/2, one or two short ones): every sample read once
-    int order[KDE_LAG_MAX];
     int nf = 0, nn = 0;
     bool folded = false;
-    if (multi && ctx->N >= 4096 && getenv("GDHIP_KDE_LAG_UNFOLDED") == nullptr) {
+    if (ctx->N >= 4096 && getenv("GDHIP_KDE_LAG_UNFOLDED") == nullptr) {
         int64_t K0 = ctx->N, nmax = 0;
         for (int i = 0; i < nlags; ++i)
             if (4 * lags[i] >= ctx->N) {
@@ -2395,36 +2391,90 @@ int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
     }
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
     GD_TRY(gd_h2d(ctx, d_c, inv4s2, (size_t)ncols * 8));
-    if (multi) {
-        const dim3 grid(nblk, ncols);
-        if (folded) {
-            gd_by_flag(ctx->w != nullptr, [&](auto HW) {
-                gd_by_flag(nn == 1, [&](auto ONE) {
-                    k_kde_lag_folded<HW.value, 5, ONE.value ? 1 : 2><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c,
-                                                                                                    d_lags, part);
-                });
+    const dim3 grid(nblk, ncols);
+    if (folded) {
+        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+            gd_by_flag(nn == 1, [&](auto ONE) {
+                k_kde_lag_folded<HW.value, 5, ONE.value ? 1 : 2><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c,
+                                                                                                d_lags, part);
             });
-        } else
-            gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+        });
+    } else
+        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
 #define KDE_LAUNCH(NLV) \
     case NLV: k_kde_lag_multi<HW.value, NLV><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c, d_lags, part); break;
-                switch (nlags) {
-                    KDE_LAUNCH(1) KDE_LAUNCH(2) KDE_LAUNCH(3) KDE_LAUNCH(4) KDE_LAUNCH(5) KDE_LAUNCH(6) KDE_LAUNCH(7) KDE_LAUNCH(8)
-                }
+            switch (nlags) {
+                KDE_LAUNCH(1) KDE_LAUNCH(2) KDE_LAUNCH(3) KDE_LAUNCH(4) KDE_LAUNCH(5) KDE_LAUNCH(6) KDE_LAUNCH(7) KDE_LAUNCH(8)
+            }
 #undef KDE_LAUNCH
-            });
-        GD_KERNEL_CHECK();
+        });
+    GD_KERNEL_CHECK();
+    return GD_OK;
+}
+
+// the partial sums of a multi-lag launch added per (column, lag) in block order
+void gd_kde_lag_sums_reduce(const gd_kde_lag_ticket* t, const double* h, double* out) {
+    for (int c = 0; c < t->ncols; ++c)
+        for (int l = 0; l < t->nlags; ++l) {
+            double sum = 0;
+            for (int b = 0; b < t->nblk; ++b) sum += h[((size_t)c * t->nblk + b) * KDE_LAG_MAX + l];
+            out[(size_t)c * t->nlags + t->order[l]] = sum;
+        }
+}
+
+static bool kde_lag_multi(int32_t nlags) { return nlags <= KDE_LAG_MAX && getenv("GDHIP_KDE_LAG_SINGLE") == nullptr; }
+
+int64_t gd_kde_lag_sums_partials(const gd_ctx* ctx, int32_t ncols, int32_t nlags) {
+    if (!ctx || ncols <= 0 || nlags <= 0 || !kde_lag_multi(nlags)) return 0;
+    return (int64_t)ncols * KDE_LAG_MAX * kde_lag_blocks(ctx, ncols, nlags, true);
+}
+
+int gd_kde_lag_sums_enqueue(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* inv4s2, const int64_t* lags,
+                            int32_t nlags, void* d_block, double* pinned, gd_kde_lag_ticket* t) {
+    GD_REQUIRE(ctx && cols && inv4s2 && lags && d_block && pinned && t && nlags > 0 && ncols > 0, "bad argument");
+    GD_REQUIRE(ctx->cols, "no samples uploaded");
+    GD_REQUIRE(kde_lag_multi(nlags), "more lags than one launch takes");
+    GD_REQUIRE_SAMPLE_COLUMNS(cols, ncols);
+    for (int i = 0; i < nlags; ++i) GD_REQUIRE(lags[i] > 0 && lags[i] < ctx->N, "lag out of range");
+    const int nblk = kde_lag_blocks(ctx, ncols, nlags, true);
+    ScratchPlan sp;  // (the caller's block holds gd_kde_lag_sums_partials doubles and 256 bytes per table and column)
+    auto part = sp.take<double>((int64_t)ncols * KDE_LAG_MAX * nblk);
+    auto d_lags = sp.take<int64_t>(nlags);
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_c = sp.take<double>(ncols);
+    GD_TRY(sp.place(d_block));
+    t->ncols = ncols, t->nlags = nlags, t->nblk = nblk;
+    GD_TRY(kde_lag_multi_launch(ctx, cols, ncols, inv4s2, lags, nlags, nblk, part, d_lags, d_idx, d_c, t->order));
+    return gd_fetch_pinned(ctx, pinned, part, (size_t)ncols * KDE_LAG_MAX * nblk * 8);
+}
+
+int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* inv4s2, const int64_t* lags,
+                          int32_t nlags, double* out) {
+    GD_REQUIRE(ctx && cols && inv4s2 && lags && out && nlags > 0 && nlags <= 64 && ncols > 0, "bad argument");
+    GD_REQUIRE(ctx->cols, "no samples uploaded");
+    GD_REQUIRE_COLUMNS(cols, ncols);
+    for (int i = 0; i < nlags; ++i) GD_REQUIRE(lags[i] > 0 && lags[i] < ctx->N, "lag out of range");
+    const bool multi = kde_lag_multi(nlags);
+    const int nblk = kde_lag_blocks(ctx, ncols, nlags, multi);
+    ScratchPlan sp;
+    auto part = sp.take<double>((int64_t)ncols * (multi ? KDE_LAG_MAX : nlags) * nblk);
+    auto d_lags = sp.take<int64_t>(nlags);
+    auto d_idx = sp.take<int32_t>(ncols);
+    auto d_c = sp.take<double>(ncols);
+    GD_TRY(sp.get(ctx));
+    if (multi) {
+        gd_kde_lag_ticket t;
+        t.ncols = ncols, t.nlags = nlags, t.nblk = nblk;
+        GD_TRY(kde_lag_multi_launch(ctx, cols, ncols, inv4s2, lags, nlags, nblk, part, d_lags, d_idx, d_c, t.order));
         std::vector<double> h((size_t)ncols * nblk * KDE_LAG_MAX);
         GD_TRY(gd_fetch(ctx, h.data(), part, h.size() * 8));
         GD_TRY(gd_stream_sync(ctx));
-        for (int c = 0; c < ncols; ++c)
-            for (int l = 0; l < nlags; ++l) {
-                double sum = 0;
-                for (int b = 0; b < nblk; ++b) sum += h[((size_t)c * nblk + b) * KDE_LAG_MAX + l];
-                out[(size_t)c * nlags + order[l]] = sum;
-            }
+        gd_kde_lag_sums_reduce(&t, h.data(), out);
         return GD_OK;
     }
+    GD_TRY(gd_h2d(ctx, d_lags, lags, (size_t)nlags * 8));
+    GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
+    GD_TRY(gd_h2d(ctx, d_c, inv4s2, (size_t)ncols * 8));
     const dim3 grid(nblk, nlags, ncols);
     gd_by_flag(ctx->w != nullptr, [&](auto HW) {
         k_kde_lag<HW.value><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c, d_lags, part);

@@ -630,6 +630,15 @@ class MCSamples(Chains):
         self._twin.__dict__.update({k: v for k, v in list(self.__dict__.items()) if k not in own})
         return self._twin
 
+    def _twin_context(self):
+        """The second lane's context (made on first use) for work that only needs its STREAM: unlike _second_lane this
+        neither deals this object's pairs to two lanes (``_nlanes`` stays) nor refreshes the twin's copy of the settings."""
+        if self._twin is None:
+            nlanes = self._nlanes
+            self._second_lane()
+            self._nlanes = nlanes
+        return self._twin.ctx
+
     def _lane_thread(self, twin):
         """The thread that drives the second lane (its own helper thread stays free for the lane's inner overlap)."""
         if self._lane_exec is None:
@@ -1222,16 +1231,20 @@ class MCSamples(Chains):
             par.ND_limit_top = lims[:, j, 1].copy()
         self._nd_limits_done = True
 
-    def _init_params(self, js, lag_probe=False):
+    def _init_params(self, js, lag_probe=False, ahead=0):
         """_initParam for several parameters with ONE batched quantile-select launch.  ``lag_probe``: the select's counting
         pass also delivers the autocovariance probe of the N_eff estimate for the same columns (one read of the samples
-        serves both; kept in ``_lag_prefetch`` for _probe_lags / the batched 2D entry)."""
+        serves both; kept in ``_lag_prefetch`` for _probe_lags / the batched 2D entry).  ``ahead``: what the library may
+        enqueue for the next batched 2D call once the quantiles are known (gd_prepare_params)."""
         todo = [j for j in dict.fromkeys(js) if not getattr(self.paramNames.names[j], "_ranges_done", False)]
         if not todo:
             return
         rc = self.range_confidence
         fracs = np.array([rc, 1 - rc] + list(np.linspace(0.1, 0.9, 9)))
         targets = np.tile(self.norm * fracs, (len(todo), 1))
+        if (lag_probe and hasattr(self.ctx, "prepare_params") and getattr(self, "_col_min", None) is not None
+                and not (self.range_ND_contour >= 0 and self.loglikes is not None)):
+            return self._init_params_native(todo, targets, ahead)
         if lag_probe:
             q, lags = self.ctx.quantiles_probe(todo, targets, self._minmax_of(todo), self.means[todo])
             q = np.asarray(q)
@@ -1284,6 +1297,35 @@ class MCSamples(Chains):
             par.has_limits = par.has_limits_top or par.has_limits_bot
             par._ranges_done = True
 
+    def _init_params_native(self, todo, targets, ahead):
+        """_init_params through gd_prepare_params: the select, the probe and the scalar tail in one native call (the same fp64
+        operations in the same order, csrc/batch2d.hpp prepare_tail); only the attributes are stored here."""
+        names = self.paramNames.names
+        pars = [names[j] for j in todo]
+        nan = np.nan
+        limits = np.array([[nan if p.limmin is None else p.limmin, nan if p.limmax is None else p.limmax] for p in pars])
+        twin = None
+        if (ahead & 2 and self._lane == 0 and self._context_factory is not None and self.weights is None
+                and len(todo) * (len(todo) - 1) // 2 >= min(64, self.CONV_TWO_STREAMS_PAIRS[0])):
+            twin = self._twin_context()  # (the batched call's second stream: the index columns are made on it)
+        q, lags, recs = self.ctx.prepare_params(
+            todo, targets, self._minmax_of(todo), self.means[todo], np.asarray(self.vars)[todo], np.asarray(self.sddev)[todo],
+            limits, [bool(p.has_limits_bot) for p in pars], [bool(p.has_limits_top) for p in pars], twin=twin,
+            fine_bins_2D=self.fine_bins_2D, auto_bandwidth=self.smooth_scale_2D < 0 and not self.use_effective_samples_2D,
+            uncorrelated_sampler=self.sampler in ("nested", "uncorrelated"), ahead=ahead if twin is not None else ahead & 1)
+        if lags is not None:
+            self._lag_prefetch = (todo, 8, _Done(lags))
+        for row, (j, par) in enumerate(zip(todo, pars)):
+            par.err = self.sddev[j]
+            par.mean = self.means[j]
+            par.param_min = self._col_min[j]
+            par.param_max = self._col_max[j]
+            par.range_min, par.range_max = recs["range_min"][row], recs["range_max"][row]
+            par.sigma_range = recs["sigma_range"][row]
+            par.has_limits_bot, par.has_limits_top = bool(recs["has_limits_bot"][row]), bool(recs["has_limits_top"][row])
+            par.has_limits = par.has_limits_top or par.has_limits_bot
+            par._ranges_done = True
+
     def prepareParams(self, params=None, neff=True):
         """
         Additive API: compute the per-parameter state every density needs (ranges, limits, sigma_range and, if
@@ -1302,8 +1344,12 @@ class MCSamples(Chains):
                  and hasattr(self.ctx, "quantiles_probe") and os.environ.get("GETDIST_AMD_FUSED_PROBE", "1") == "1"
                  and all(not getattr(self.paramNames.names[j], "_ranges_done", False) for j in todo))
         if fused:
+            # neff=False: the caller does not wait for N_eff here -- the library may start its lag sums (and the index columns
+            # of the base grid) behind the select, for the batched 2D call to pick up (GDHIP_PREPARE_AHEAD=0: it does not)
+            ahead = 3 if (not neff and getattr(self, "_neff_share", None) is None
+                          and os.environ.get("GDHIP_PREPARE_AHEAD", "1") != "0") else 0
             with _Phase(self, "prep.ranges"):
-                self._init_params(js, lag_probe=True)
+                self._init_params(js, lag_probe=True, ahead=ahead)
         elif (todo and self._lane == 0 and not self._timing and self.sampler not in ("nested", "uncorrelated")
                 and len(todo) >= 2 and os.environ.get("GETDIST_AMD_OVERLAP_NEFF", "1") == "1"):
             # the autocovariance probe of the N_eff estimate depends on the means only: start it on the second context

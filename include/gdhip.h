@@ -1086,6 +1086,44 @@ int gd_batch2d_invalidate(gd_ctx* ctx);
  * repeats it ("exactly once per rank and step"; the reference has no such exchange: mcsamples.py:1230-1235 is per process). */
 int gd_batch2d_exchanges(gd_ctx* ctx, int64_t* count_out);
 
+/* The per-parameter preparation of the densities (MCSamples._initParam for a list of whole sample columns) in one call:
+ * the quantile select with the autocovariance probe riding on it (exactly gd_quantiles_mm_probe with 11 targets per column:
+ * the range_confidence quantile, its mirror, the deciles 0.1 .. 0.9), then the scalar tail in fp64 with Python's own
+ * operations in Python's order: spans of four deciles, scale / 1.049, the flat test, sigma_range, the limit decisions
+ * against smooth_1D, the widened ranges.  recs[c] arrives with has_limits_bot / has_limits_top as the prior ranges set them
+ * (limits: ncols x 2, the prior bounds where the flags are set) and leaves final.
+ *
+ * With settings->ahead the entry then ENQUEUES, without waiting, what the next gd_density2d_batch over these columns starts
+ * with, because it needs nothing but what is known here:
+ *   - the byte-index columns of the base grid (fine_bins_2D = 256, enough columns for the 64 pairs of the byte-index route;
+ *     unit weights only -- a sample set with real weights, which the batched call also bins from byte indices, gets the lag
+ *     sums alone) on `twin`'s stream, into the index-column cache of ctx's batched calls;
+ *   - behind them, on ctx's own stream, the first launch of the N_eff lag sums (automatic bandwidths, a correlated sampler,
+ *     probe delivered, no chain that outlasts it), partial sums copied to page-locked memory by a kernel behind the launch.
+ * gd_density2d_batch uses a piece when its own arguments are the same to the bit (the columns -- in any order --, their
+ * kernel widths, the lags, N; bin minimum and width per column) -- results are those of a call without the pieces, bit for
+ * bit: the partial sums are added per column in the same block order -- and otherwise waits for the
+ * piece's event, discards it and proceeds as it would have.  Every replacement of the samples or weights and gd_destroy drop
+ * pending pieces after their events.  GDHIP_PREPARE_AHEAD=0 in the environment: nothing is enqueued ahead. */
+typedef struct gd_prepared_param {
+    double range_min, range_max, sigma_range;
+    int32_t has_limits_bot, has_limits_top;
+} gd_prepared_param;
+
+typedef struct gd_prepare_settings {
+    int32_t fine_bins_2D;
+    int32_t auto_bandwidth;       /* smooth_scale_2D < 0 and nothing injected: the batched call will want N_eff */
+    int32_t uncorrelated_sampler; /* sampler "nested" / "uncorrelated": N_eff needs no lag sums */
+    int32_t ahead;                /* bit 0: the N_eff lag sums, bit 1: the index columns */
+} gd_prepare_settings;
+
+int gd_prepare_params(gd_ctx* ctx, gd_ctx* twin, const gd_prepare_settings* settings, const int32_t* cols, int32_t ncols,
+                      const double* targets, const double* minmax, const double* means, const double* vars, const double* err,
+                      const double* limits, double* quantiles_out, double* probe_out, int32_t* probe_done,
+                      gd_prepared_param* recs);
+/* out3 = pieces enqueued ahead, consumed by a batched call, discarded (mismatch, edit, teardown) on this context so far */
+int gd_prepare_ahead_counts(gd_ctx* ctx, int64_t* out3);
+
 
 /* ---------------------------------------------------------------- multi-GPU: RCCL over xGMI ------------------------
  * One process per GPU.  The path has no data-path collective: pairs are partitioned and every rank copies
