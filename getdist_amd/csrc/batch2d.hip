@@ -73,9 +73,7 @@ std::vector<const void*> settle_prebin(gd_ctx* owner, Ahead& A, bool used, const
         if (ran && A.bad_pinned[A.bad_pinned[m + c]] == 0) continue;
         bad.push_back(buf);
         if (std::find(rebinned.begin(), rebinned.end(), buf) != rebinned.end()) continue;
-        std::lock_guard<std::mutex> gs(st.mu);
-        auto it = st.idx.find(std::make_tuple((int)A.prebin.cols[c], 256, 1));
-        if (it != st.idx.end() && it->second.ptr == buf) it->second.valid = false;
+        gdb::IndexCache{st}.mark_stale((int)A.prebin.cols[c], 256, gdb::IndexCache::kBytes, buf);
     }
     A.prebin.pending = false;
     {
@@ -357,9 +355,8 @@ int enqueue_prebin_ahead(gd_ctx* ctx, gd_ctx* twin, Ahead& A, const int32_t* col
                          const gd_prepared_param* recs) {
     gdb::State& st = state_of(ctx);
     gdb::Pool pool{st, kOps, ctx};
-    std::vector<int32_t> todo;
+    std::vector<int32_t> want;
     std::vector<double> b0, w;
-    std::vector<void*> bufs;
     for (int c = 0; c < ncols; ++c) {
         gd_param2d p;
         memset(&p, 0, sizeof p);
@@ -369,23 +366,13 @@ int enqueue_prebin_ahead(gd_ctx* ctx, gd_ctx* twin, Ahead& A, const int32_t* col
         gdb::bin_edges(p, &lo, &hi);
         const double fw = (hi - lo) / 255;
         if (!(fw > 0) || !std::isfinite(fw) || !std::isfinite(lo)) continue;
-        gdb::IdxCol col;
-        {
-            std::lock_guard<std::mutex> g(st.mu);
-            col = st.idx[std::make_tuple((int)cols[c], 256, 1)];
-        }
-        if (col.valid && col.binmin == lo && col.width == fw) continue;
-        if (!col.ptr) {
-            int rc = 0;
-            col.ptr = pool.take(ctx->N + 64, &rc);
-            if (!col.ptr) return rc;
-            std::lock_guard<std::mutex> g(st.mu);
-            gdb::IdxCol& e = st.idx[std::make_tuple((int)cols[c], 256, 1)];
-            e.ptr = col.ptr, e.valid = false;
-        }
-        todo.push_back(cols[c]), b0.push_back(lo), w.push_back(fw), bufs.push_back(col.ptr);
+        want.push_back(cols[c]), b0.push_back(lo), w.push_back(fw);
     }
-    const int m = (int)todo.size();
+    gdb::IndexCache cache{st};
+    gdb::IndexCache::Stale stale;
+    int rc = cache.stale(pool, want, 256, gdb::IndexCache::kBytes, ctx->N, b0.data(), w.data(), stale);
+    if (rc) return rc;
+    const int m = (int)stale.cols.size();
     if (!m) return 0;
     if (A.bad_words < 2 * (int64_t)m) {
         if (A.bad_pinned) (void)hipHostFree(A.bad_pinned);
@@ -395,24 +382,18 @@ int enqueue_prebin_ahead(gd_ctx* ctx, gd_ctx* twin, Ahead& A, const int32_t* col
     }
     memset(A.bad_pinned, 0xff, (size_t)m * 8);  // (a count that never arrives reads as out of range)
     if (!A.ev_prebin && hipEventCreateWithFlags(&A.ev_prebin, hipEventDisableTiming) != hipSuccess) return GD_ERR_HIP;
-    int rc = gd_prebin8_enqueue(twin, todo.data(), m, b0.data(), w.data(), bufs.data(), A.bad_pinned);
+    rc = gd_prebin8_enqueue(twin, stale.cols.data(), m, stale.binmin.data(), stale.width.data(), stale.bufs.data(), A.bad_pinned);
     // (whatever was enqueued before a failure still writes the columns: the event goes behind it either way)
     const bool recorded = hipEventRecord(A.ev_prebin, twin->stream) == hipSuccess;
     if (rc || !recorded) {
         (void)hipStreamSynchronize(twin->stream);
         return rc ? rc : GD_ERR_HIP;
     }
-    {
-        std::lock_guard<std::mutex> g(st.mu);
-        for (int q = 0; q < m; ++q) {
-            gdb::IdxCol& e = st.idx[std::make_tuple((int)todo[q], 256, 1)];
-            e.binmin = b0[q], e.width = w[q], e.valid = true;
-        }
-    }
-    A.prebin.cols = todo, A.prebin.bufs = bufs, A.prebin.pending = true;
+    cache.commit(stale, 256, gdb::IndexCache::kBytes);  // (the counts arrive with the event: settle_prebin)
+    A.prebin.cols = stale.cols, A.prebin.bufs = stale.bufs, A.prebin.pending = true;
     {
         std::lock_guard<std::mutex> g(g_prebin_mu);
-        for (void* buf : bufs) g_prebin_owner[buf] = ctx;
+        for (void* buf : stale.bufs) g_prebin_owner[buf] = ctx;
     }
     ++A.enqueued;
     return 0;

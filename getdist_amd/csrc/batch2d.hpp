@@ -16,11 +16,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -29,6 +29,8 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/gdhip.h"
@@ -86,7 +88,8 @@ struct Ops {
     // the context's communicator (gd_comm_init): number of ranks (0: none) / sum all-reduce of a host vector
     int (*comm_world)(void* h);
     int (*comm_allreduce_sum)(void* h, double* inout, int64_t count);
-    // the (idle) context's stream re-created with high (1) / normal (0) / low (-1) priority
+    // the (idle) context's stream re-created with high (1) / normal (0) / low (-1) priority.  The call itself no longer uses it
+    // (create_aux gives its contexts their priority); the slot stays so that the table keeps the layout its binders know
     int (*stream_priority)(void* ctx, int level);
     // u16 index columns of several sample columns in ONE launch (gd_prebin_batch; blocking).  May be null: `prebin` per column
     int (*prebin_batch)(void* h, const int32_t* cols, int32_t ncols, const double* binmin, const double* width, int32_t F,
@@ -230,6 +233,18 @@ static inline void prepare_tail(const double q[11], double col_min, double col_m
 // both read: the fewest pairs of the base grid's class that take the byte-index route, and min_corr of the N_eff estimate.
 static constexpr int kByteIndexMinPairs = 64;
 static constexpr double kNeffMinCorr = 0.05;
+// The choreography's fixed choices (each was a tuning knob while it was measured; the figures are in DESIGN.md §1 and §8).
+// Two optimiser parts: the second's DCT / fixed point beside the first's get_h and convolution.  More, smaller parts were
+// measured (3 / 4 / 12: 31.2 / 32.1 / 31.4 ms per C3 step against 30.5 with two): the chip is busy either way, and a part
+// below two blocks per CU leaves the fixed-point kernel's tail exposed.
+static constexpr size_t kKoptParts = 2;
+// The fixed-point kernel holds one pair per CU (its matrix lives in the CU's registers and LDS): parts of a whole number of
+// rounds over the 256 CUs leave no extra, mostly empty round (1279 pairs as 640 + 639 are 3 + 3 rounds, as 512 + 767: 2 + 3).
+static constexpr size_t kKoptPartAlign = 256;
+// What the N_eff launch waits once the binning chain is being enqueued (its launches go out)
+static constexpr int kNeffHoldUs = 120;
+// Pairs of a call's first convolution batch / of every other one, where the settings leave them open
+static constexpr int kFirstBatch = 128, kMaxBatch = 320;
 
 // ---- effective sample numbers (chains.py:477-574 via mcsamples.py:1230-1235) -------------------------------------------
 struct NeffInput {
@@ -424,10 +439,10 @@ struct State {
     std::vector<std::pair<void*, int64_t>> free_blocks;  // (device pointer, capacity)
     std::map<void*, int64_t> capacity;                   // of every block handed out
     int64_t cached_bytes = 0;
-    std::map<std::tuple<int, int, int>, IdxCol> idx;     // (column, F, 1 = bytes / 2 = u16)
+    std::map<std::tuple<int, int, int>, IdxCol> idx;     // (column, F, kind): read and written through IndexCache only
     Pending prev;                                        // the last lazily delivered call
     void* aux = nullptr;                                 // third context (stream) of large calls: shear chain, get_h
-    void* aux2 = nullptr;                                // fourth: the DEFERRED shear chain + up-scaled classes (round 6)
+    void* aux2 = nullptr;                                // fourth: the DEFERRED shear chain + up-scaled classes
     // work the preparation entry (gd_prepare_params) enqueued ahead of the next batched call: the binding's own record
     // (batch2d.hip), and whether N_eff lag sums are among it (neff_batch then has nothing to hold back)
     void* ahead = nullptr;
@@ -493,6 +508,82 @@ struct Pool {
         }
         for (auto& b : blocks) ops.dev_free(h, b.first);
     }
+    // a block that goes back to the pool when the scope ends, unless somebody has taken it over by then
+    struct Lease {
+        Pool& pool;
+        void* p;
+        ~Lease() { pool.give(p); }
+        void* keep() { return std::exchange(p, nullptr); }
+    };
+};
+
+// The index columns of the resident samples, cached per (column, grid size, kind) with the edges they were binned with.
+// A column's block is published as the column's own -- not yet valid -- BEFORE any launch writes it, and becomes valid when
+// the launch has been committed: a launch that fails leaks nothing and leaves nothing valid behind.
+struct IndexCache {
+    enum Kind { kBytes = 1, kU16 = 2 };  // (also the bytes per sample)
+    State& st;
+    struct Stale {
+        std::vector<int32_t> cols;
+        std::vector<double> binmin, width;
+        std::vector<void*> bufs;
+    };
+    // the columns of `cols` (edges binmin / width, parallel to it) that are not cached with these edges, each with its block
+    // of N samples (from `pool` where it has none); 0, or the code of the allocation that failed
+    int stale(Pool& pool, const std::vector<int32_t>& cols, int F, Kind kind, int64_t N, const double* binmin, const double* width,
+              Stale& out) {
+        for (size_t q = 0; q < cols.size(); ++q) {
+            const auto key = std::make_tuple((int)cols[q], F, (int)kind);
+            IdxCol c;
+            {
+                std::lock_guard<std::mutex> g(st.mu);
+                c = st.idx[key];
+            }
+            if (c.valid && c.binmin == binmin[q] && c.width == width[q]) continue;
+            if (!c.ptr) {
+                int rc = 0;
+                c.ptr = pool.take(N * (int)kind + 64, &rc);
+                if (!c.ptr) return rc;
+            }
+            {
+                std::lock_guard<std::mutex> g(st.mu);
+                IdxCol& e = st.idx[key];
+                e.ptr = c.ptr, e.valid = false;
+            }
+            out.cols.push_back(cols[q]), out.binmin.push_back(binmin[q]), out.width.push_back(width[q]), out.bufs.push_back(c.ptr);
+        }
+        return 0;
+    }
+    // after the launch that wrote them: the edges, and valid -- on the byte route (`bad`: samples outside the grid per
+    // column) only a column that holds every sample
+    void commit(const Stale& done, int F, Kind kind, const int64_t* bad = nullptr) {
+        std::lock_guard<std::mutex> g(st.mu);
+        for (size_t q = 0; q < done.cols.size(); ++q) {
+            IdxCol& c = st.idx[std::make_tuple((int)done.cols[q], F, (int)kind)];
+            c.binmin = done.binmin[q], c.width = done.width[q], c.valid = !bad || bad[q] == 0;
+        }
+    }
+    void* lookup(int col, int F, Kind kind) {
+        std::lock_guard<std::mutex> g(st.mu);
+        auto it = st.idx.find(std::make_tuple(col, F, (int)kind));
+        return it == st.idx.end() ? nullptr : it->second.ptr;
+    }
+    // a column found bad after it was committed (work enqueued ahead): stale, if `ptr` is still its block
+    void mark_stale(int col, int F, Kind kind, const void* ptr) {
+        std::lock_guard<std::mutex> g(st.mu);
+        auto it = st.idx.find(std::make_tuple(col, F, (int)kind));
+        if (it != st.idx.end() && it->second.ptr == ptr) it->second.valid = false;
+    }
+    void invalidate() {  // the samples changed: every column keeps its block and is binned again
+        std::lock_guard<std::mutex> g(st.mu);
+        for (auto& kv : st.idx) kv.second.valid = false;
+    }
+    void release() {  // every block back to the pool
+        std::lock_guard<std::mutex> g(st.mu);
+        for (auto& kv : st.idx)
+            if (kv.second.ptr) st.free_blocks.emplace_back(kv.second.ptr, st.capacity[kv.second.ptr]);
+        st.idx.clear();
+    }
 };
 
 static inline int complete_pending(State& st, const Ops& ops, void* h, Pending& pd) {
@@ -509,21 +600,13 @@ static inline int complete_pending(State& st, const Ops& ops, void* h, Pending& 
 
 static inline int finish_all(State& st, const Ops& ops, void* h) { return complete_pending(st, ops, h, st.prev); }
 
-static inline void invalidate_index_columns(State& st) {
-    std::lock_guard<std::mutex> g(st.mu);
-    for (auto& kv : st.idx) kv.second.valid = false;
-}
+static inline void invalidate_index_columns(State& st) { IndexCache{st}.invalidate(); }
 
 // frees every device block the state holds (context teardown / new sample set)
 static inline void release_all(State& st, const Ops& ops, void* h) {
     finish_all(st, ops, h);
     Pool pool{st, ops, h};
-    {
-        std::lock_guard<std::mutex> g(st.mu);
-        for (auto& kv : st.idx)
-            if (kv.second.ptr) st.free_blocks.emplace_back(kv.second.ptr, st.capacity[kv.second.ptr]);
-        st.idx.clear();
-    }
+    IndexCache{st}.release();
     pool.drop_cached();
     if (st.aux) {  // (attached to the sample set that is going away)
         ops.destroy_aux(st.aux);
@@ -535,7 +618,162 @@ static inline void release_all(State& st, const Ops& ops, void* h) {
     }
 }
 
+// ---- hand-offs between the threads of a call --------------------------------------------------------------------------
+// Every wait of the choreography is a sleeping poll: the quanta and bounds were tuned with the wake-up latency on the
+// critical path.  quantum_us 0: yield instead of sleeping; bound_us 0: until ready.  False: the bound passed.
+template <class Ready>
+static inline bool poll_until(const Ready& ready, int quantum_us, int64_t bound_us) {
+    const auto t0 = std::chrono::steady_clock::now();
+    while (!ready()) {
+        if (bound_us > 0 && std::chrono::steady_clock::now() - t0 >= std::chrono::microseconds(bound_us)) return false;
+        quantum_us > 0 ? std::this_thread::sleep_for(std::chrono::microseconds(quantum_us)) : std::this_thread::yield();
+    }
+    return true;
+}
+
+// One thread tells others that something exists.  A gate opens once, with a code (0: what the consumer waits for is
+// there), and stays open.  Its producer holds an Opener: when the producer's scope ends -- return, early return or
+// exception -- a gate that is still closed opens with the code the producer left (GD_ERR_HIP if none).  A wait without a
+// bound is served only on a gate that has an Opener, which therefore has to exist before the consumer can start waiting
+// (start() makes it in the thread that starts the producer); on any other gate such a wait fails at once instead of hanging.
+class Gate {
+    static constexpr int kClosed = INT_MIN;
+    std::atomic<int> state_{kClosed};
+    std::atomic<bool> held_{false};
+
+public:
+    void open(int code = 0) {
+        int closed = kClosed;
+        state_.compare_exchange_strong(closed, code, std::memory_order_release, std::memory_order_relaxed);
+    }
+    bool is_open() const { return state_.load(std::memory_order_acquire) != kClosed; }
+    int code() const { return state_.load(std::memory_order_acquire); }  // of an open gate
+    // true: the gate is open (code() is what the producer left)
+    bool wait(int quantum_us, int64_t bound_us) const {
+        if (bound_us <= 0 && !held_.load() && !is_open()) return false;
+        return poll_until([this] { return is_open(); }, quantum_us, bound_us);
+    }
+    class Opener {
+        Gate* gate_;
+        int code_ = GD_ERR_HIP;
+
+    public:
+        explicit Opener(Gate* g = nullptr) : gate_(g) {
+            if (g) g->held_.store(true);
+        }
+        Opener(Opener&& o) noexcept : gate_(o.gate_), code_(o.code_) { o.gate_ = nullptr; }
+        void leave(int code) { code_ = code; }  // what the gate opens with if nobody has opened it when the scope ends
+        ~Opener() {
+            if (gate_) gate_->open(code_);
+        }
+    };
+};
+
+// A thread of the call and the one place its result is read: whoever needs it first waits for the thread, everyone
+// after that gets the same code.
+struct Worker {
+    std::future<int> result;
+    std::mutex mu;
+    int rc = 0;
+    int join(bool* was_running = nullptr) {
+        std::lock_guard<std::mutex> g(mu);
+        if (was_running) *was_running = result.valid();
+        if (result.valid()) rc = result.get();
+        return rc;
+    }
+};
+
+template <class F>
+struct AtExit {  // f runs when the scope ends, however it ends
+    F f;
+    ~AtExit() { f(); }
+};
+template <class F>
+AtExit(F) -> AtExit<F>;
+
+// ---- the optimiser's launches ------------------------------------------------------------------------------------------
+struct Launch {
+    int F = 0;
+    std::vector<int> ks;   // plan indices in batch order
+    int na = 0;            // leading sheared rows
+    void* d_hist = nullptr;  // class buffer (the sheared histograms when the launch holds nothing else)
+    std::vector<int> pos;  // positions within the class buffer of the non-sheared rows
+    bool whole = false;    // the buffer as it lies
+    // staged mode
+    void* d_batch = nullptr;
+    bool own = false;
+    void* d_rows = nullptr;
+    int32_t ticket = -1;
+    std::vector<double> ne, fb, ci;
+    std::vector<int32_t> dc;
+};
+
+// the size of a part of the base grid's optimiser launches (total = its own pairs + the sheared pairs)
+static inline size_t base_part_size(size_t total, int F, int split_min) {
+    size_t part = std::max<size_t>((size_t)split_min, (total + kKoptParts - 1) / kKoptParts);
+    if (F == 256 && part > kKoptPartAlign) part = std::max(kKoptPartAlign, (part + kKoptPartAlign / 2 - 1) / kKoptPartAlign * kKoptPartAlign);
+    return part;
+}
+
+// The optimiser's launches of a call, from the plan alone (no device call; d_hist is the caller's to fill): one launch per
+// grid-size class that has optimiser pairs (branch C), in class order; `staged` cuts the base grid's launch into parts.  The
+// sheared pairs (branch A) lead one launch of the base class -- the first, or with the deferred chain the last, which then
+// takes whatever is left -- or make a launch of their own when the base class has no optimiser pairs.
+static inline std::vector<Launch> plan_launches(const std::vector<int8_t>& branch, const std::vector<int>& F_list,
+                                                const std::map<int, std::vector<int>>& classes, int base_F, bool staged,
+                                                bool shear_deferred, int split_min) {
+    std::vector<int> A;
+    for (int k = 0; k < (int)branch.size(); ++k)
+        if (branch[k] == 0) A.push_back(k);
+    const int nA = (int)A.size();
+    std::vector<Launch> launches;
+    bool merged = false;
+    for (int F : F_list) {
+        const std::vector<int>& mem = classes.at(F);
+        std::vector<int> pos_C;
+        for (int q = 0; q < (int)mem.size(); ++q)
+            if (branch[mem[q]] == 2) pos_C.push_back(q);
+        if (pos_C.empty()) continue;
+        const bool base = F == base_F;  // (any other class: one launch of its own pairs)
+        const size_t total = pos_C.size() + (base ? (size_t)nA : 0);
+        const size_t part = (base && staged && (int)pos_C.size() >= split_min) ? base_part_size(total, F, split_min) : total;
+        const size_t nparts = std::max<size_t>(1, (total + part - 1) / part);
+        for (size_t c0 = 0, ip = 0; c0 < pos_C.size(); ++ip) {
+            Launch L;
+            const bool carries = shear_deferred ? (ip + 1 == nparts || pos_C.size() - c0 <= part) : ip == 0;
+            L.F = F, L.na = (base && carries) ? nA : 0;
+            size_t take = std::min(pos_C.size() - c0, part > (size_t)L.na ? part - (size_t)L.na : (size_t)1);
+            if (shear_deferred && carries) take = pos_C.size() - c0;
+            L.pos.assign(pos_C.begin() + c0, pos_C.begin() + c0 + take);
+            c0 += take;
+            L.whole = L.na == 0 && L.pos.size() == mem.size();
+            for (int q = 0; q < L.na; ++q) L.ks.push_back(A[q]);
+            for (int q : L.pos) L.ks.push_back(mem[q]);
+            launches.push_back(std::move(L));
+        }
+        merged = merged || base;
+    }
+    if (nA && !merged) {
+        Launch L;
+        L.F = base_F, L.na = nA, L.whole = true, L.ks = A;
+        launches.push_back(std::move(L));
+    }
+    return launches;
+}
+
 // ---- the call ----------------------------------------------------------------------------------------------------------
+// The environment switches of a call, read once when the call is made (tests set them between calls of one process).
+struct Switches {
+    bool log = getenv("GDHIP_BATCH_LOG") != nullptr;  // the host timeline on stderr when the call returns
+    // the reference paths of the tests: the chain joined in front of the optimiser (=0) / its threshold in pairs / one binning launch
+    bool shear_deferred = !getenv("GDHIP_BATCH_SHEAR_DEFERRED") || atoi(getenv("GDHIP_BATCH_SHEAR_DEFERRED")) != 0;
+    int shear_deferred_min = getenv("GDHIP_BATCH_SHEAR_DEFERRED_MIN") ? atoi(getenv("GDHIP_BATCH_SHEAR_DEFERRED_MIN")) : 256;
+    bool one_binning = getenv("GDHIP_BATCH_ONE_BINNING") != nullptr;
+    // test hook: a slow second half of the chain
+    int side_binning_delay_ms = getenv("GDHIP_BATCH_TEST_SIDE_BINNING_DELAY_MS") ? atoi(getenv("GDHIP_BATCH_TEST_SIDE_BINNING_DELAY_MS")) : 0;
+    bool no_wsort = getenv("GDHIP_NO_WSORT") != nullptr;  // real weights: no byte-index route
+};
+
 struct Call {
     State& st;
     const Ops& ops;
@@ -565,159 +803,111 @@ struct Call {
          double* levels_, int32_t* level_status_)
         : st(st_), ops(ops_), h(h_), twin(twin_), s(s_), par(par_), n(n_), corrmat(corr_), cov(cov_), lag_probe(lag_probe_),
           pairs(pairs_), P(P_), exchange(ex_), exchange_user(ex_user_), grids(grids_), grids_doubles(grids_doubles_),
-          status_pinned(status_), meta(meta_), levels(levels_), level_status(level_status_), pool{st_, ops_, h_} {}
+          status_pinned(status_), meta(meta_), levels(levels_), level_status(level_status_), pool{st_, ops_, h_}, cache{st_} {}
+    // (an exception on the calling thread: no thread of the call outlives what it works on)
+    ~Call() {
+        conv.first_enqueued.open();
+        (void)neff.join(), (void)bin.thread.join(), (void)shear.thread.join();
+    }
 
+    const Switches env;
     int64_t N = 0;
     bool unit_weights = true;
+    bool byte_index_weights = false;  // real weights: the byte-index route is served too (gd_hist2d_prebinned8's sorted form)
     Pool pool;
+    IndexCache cache;
     PairScalars ps;
     std::vector<int> used;
     std::vector<double> bmin, bmax;  // per column
     std::vector<double> fwx, fwy;    // per pair
     std::vector<int> F_list;         // grid sizes in order of first appearance
     std::map<int, std::vector<int>> classes;  // F -> pair indices, ascending
-    std::map<int, void*> hists;               // F -> device histograms of the class, in member order
+    std::map<int, void*> hists;               // F -> device histograms of the class, in member order (under enq_mu)
+    std::mutex enq_mu;
     Plan plan;
+    std::vector<double> rx, ry, cc, smooth, W;  // per pair; W: P x 3
+    std::vector<int64_t> winw;
+    std::vector<int32_t> flags, group;
+    void* aux = nullptr;  // third context (large calls)
+    Worker neff;          // the N_eff thread of a large call
+
+    // Main binning, on the second context beside the N_eff kernels.
+    struct Binning {
+        Worker thread;
+        // The N_eff launch (2000 resident blocks for ~3 ms: whatever is enqueued behind it on another stream waits for a wave
+        // slot) holds back until the binning thread is enqueuing its chain: the binning is on the critical path, the N_eff
+        // values are needed after it (a race the binning used to win by ~0.2 ms).
+        Gate launching;
+        bool hold_neff = false;
+        // Two launches (single-triangle latency): the members of the base grid's class are put in the order the optimiser
+        // takes them (its own pairs first, the sheared and rule-of-thumb pairs behind), rows [0, first_rows) -- the FIRST
+        // optimiser part's -- are binned by the fused prebin + histogram call, the other rows by a second histogram launch
+        // behind it, and stage A of the first part starts when the first launch has run instead of waiting for both.
+        // Everything else (the later parts, every convolution, the deferred chain) joins the whole binning.  A pair's histogram
+        // does not depend on its row or on the launch that fills it: results unchanged bit for bit.  first_rows 0: one launch.
+        int first_rows = 0;
+        Gate first_run;  // the first launch has run (or the thread has ended)
+        Gate done;       // the thread has ended: the whole main binning has run
+        std::vector<void*> stale;  // a class buffer whose second launch failed (under enq_mu; freed with the call's blocks)
+    } bin;
+
+    // Branch A's chain -- min/max of the sheared coordinate, re-binning of the fp64 samples -- and the up-scaled grid classes
+    // behind it, on the third context.  Deferred (single-triangle latency): the first result copies can leave once the FIRST
+    // optimiser part's pairs are convolved, and 642 MB of grids then take ~13 ms of PCIe, so what that first part waits for
+    // decides when a triangle is delivered.  The chain then runs on a context of its own, its pairs ride in the LAST base
+    // part, and the staging thread waits for it only when it builds the first launch that needs it.  Results are unchanged
+    // bit for bit (a pair's grid does not depend on the part it is computed in).
     struct Shear {
         void* d_rot = nullptr;
         std::vector<int> A;
         std::vector<double> r1s, r2s;
+        bool have = false;
+        Worker thread;
+        bool deferred = false;
+        bool running = false;  // a deferred chain that the optimiser's launches may have to wait for
+        // The chain's two halves are awaited separately: a launch that carries sheared rows needs the SHEARED HISTOGRAMS only,
+        // not the up-scaled classes binned behind them -- the last base part's stage A used to start 2.5 ms later than its rows
+        // existed (stream timeline of a C3 step: sheared histograms done at 16.9 ms, the up-scaled classes at 19.4, the last
+        // part's first kernel at 19.6).  Opens with the code of shear_histograms.
+        Gate hists;
     } shear;
-    bool have_shear = false;
-    bool byte_index_weights = false;  // real weights: the byte-index route is served too (round 6: gd_hist2d_prebinned8's sorted form)
-    // convolution state
-    std::vector<double> rx, ry, cc, smooth, W;  // W: P x 3
-    std::vector<int64_t> winw;
-    std::vector<int32_t> flags, group;
-    std::vector<void*> call_blocks;  // everything to release once the copies have landed
-    std::vector<void*> bin_stale;    // a main-class buffer whose second launch failed (under enq_mu; joins call_blocks)
-    std::mutex enq_mu;
-    // three-stream choreography: the N_eff launch (2000 resident blocks for ~3 ms: whatever is enqueued behind it on another
-    // stream waits for a wave slot) holds back until the binning thread is about to enqueue its chain -- the binning is on
-    // the critical path, the N_eff values are needed after it (round 6: a race the binning used to win by ~0.2 ms)
-    std::atomic<int> bin_launching{0};
-    bool hold_neff_for_binning = false;
-    // the sheared pairs (and the up-scaled grid classes behind them) are convolved LAST: their O(N) chain -- as long as the
-    // main class's -- may wait until the main binning has run instead of sharing the machine with it (the main class's
-    // histograms gate the optimiser and with it the first result copies: single-triangle latency)
-    std::atomic<int> bin_done{0};
-    bool shear_after_binning = false;
-    // Deferred shear chain (round 6, single-triangle latency): the first result copies can leave once the FIRST optimiser
-    // part's pairs are convolved, and 642 MB of grids then take ~13 ms of PCIe -- so what that first part has to wait for
-    // decides when a triangle is delivered.  The sheared pairs (branch A: min/max of the sheared coordinate, a re-binning pass
-    // over the fp64 samples) and the up-scaled grid classes used to be joined BEFORE any optimiser launch and the sheared pairs
-    // rode in the first part; now their chain runs on a context of its own, starts when the main class has been binned,
-    // the sheared pairs ride in the LAST base part, and the main thread joins the chain only when it builds the first launch
-    // that needs it.  Results are unchanged bit for bit (a pair's grid does not depend on the part it is computed in).
-    std::future<int> shear_future;
-    bool shear_deferred = false;
-    std::atomic<bool> shear_joined{true};
-    std::mutex shear_mu;  // (join_shear is entered by the staging thread and, for the last report, by the enqueuing thread)
-    // The chain's two halves are awaited separately: a launch that carries sheared rows needs the SHEARED HISTOGRAMS only
-    // (shear_hist_state: 0 running, 1 done, 2 failed with shear_hist_rc), not the up-scaled grid classes the chain bins behind
-    // them -- the last base part's stage A used to start 2.5 ms later than its rows existed (stream timeline of a C3 step:
-    // sheared histograms done at 16.9 ms, the up-scaled classes at 19.4, the last part's first kernel at 19.6).
-    std::atomic<int> shear_hist_state{1};
-    int shear_hist_rc = 0;
-    // ... and it starts only when the FIRST optimiser part's convolution has been enqueued (its stage A, get_h and first
-    // batches get the machine ahead of the chain's 1024-thread blocks; the chain then runs beside the later parts): same-box
-    // A/B, delivered triangle: chain at once 29.4-29.9 ms, released on the first part's bandwidths 28.8-29.5, on its
-    // convolution 28.1-28.9; the stream of triangles 21.7 -> 21.9.  Released at once when the first launch itself needs the
-    // chain, when nothing is staged, and on every error path (and after 20 ms whatever happens).
-    std::atomic<int> first_part_done{0};
-    // ... and, since the end of round 6, only when that convolution has RUN: the chain's 1024-thread blocks take every CU for
-    // ~3 ms, and started on the enqueue they ran beside the first part's convolution -- the triangle's first grids, which the
-    // 13 ms of result copies wait for.  Found through a profiler artefact: under rocprofv3's kernel trace the enqueue of the
-    // first batches takes 2.5 ms instead of 0.3, the chain started that much later, and a delivered triangle took 24.6 ms instead
-    // of 26.5 (the stream of triangles 22.4 instead of 19.9).  A timed hold showed the same (GDHIP_BATCH_SHEAR_HOLD_US = 1000 /
-    // 2000 / 3000 / 4500: delivered 26.1 / 24.6 / 24.5 / 24.3 ms, stream 20.4 / 20.6 / 21.6 / 22.2 against 26.5 / 19.9 without).
-    // The release is the status word of the first report's last batch: enqueue_batch pre-sets a batch's words to a sentinel, the
-    // batch's last launch (a copy kernel into page-locked memory) overwrites them, and the chain's thread polls the word.
-    // GDHIP_BATCH_SHEAR_ON_ENQUEUE=1: the release of the enqueue, as before -- which is also what a STREAM of calls gets
-    // (settings.results_in_flight: this call's first grids queue behind the previous call's copies, its delivery does not wait
-    // for them, and the chain beside the first convolution is the better use of the machine: 19.9 against 21.0 ms per triangle).
-    static constexpr int32_t kStatusPending = 0x7fffffff;
-    std::atomic<const volatile int32_t*> first_part_flag{nullptr};
-    int reports_enqueued = 0;  // (enqueuing thread only)
-    // Main binning in two launches (round 6, single-triangle latency): the members of the base grid's class are put in the
-    // order the optimiser takes them (its own pairs first, the sheared and rule-of-thumb pairs behind), the rows of the FIRST
-    // optimiser part are binned by the fused prebin + histogram call, the other rows by a second histogram launch behind it
-    // -- and stage A of the first part starts when the first launch has run instead of waiting for both.  Everything else
-    // (the later parts, every convolution, the deferred chain) joins the whole binning as before.  A pair's histogram does
-    // not depend on its row or on the launch that fills it: results unchanged bit for bit.
-    std::shared_future<int> bin_future;
-    std::mutex bin_mu;
-    std::atomic<int> bins_first_done{0};
-    int bins_first_rows = 0;  // rows [0, bins_first_rows) of the main class's buffer are the first launch's; 0: one launch
-    int bin_rc = 0;
-    bool bin_joined = true;
-    int join_binning() {
-        std::lock_guard<std::mutex> g(bin_mu);
-        if (!bin_joined) {
-            bin_joined = true;
-            bin_rc = bin_future.valid() ? bin_future.get() : 0;
-            mark("binning: joined");
-        }
-        return bin_rc;
-    }
-    // the size of a part of the base grid's optimiser launches (total = its own pairs + the sheared pairs)
-    size_t base_part_size(size_t total, int F) const {
-        // Two parts: the second's DCT / fixed point beside the first's get_h and convolution.  More, smaller
-        // parts were measured (3 / 4 / 12: 31.2 / 32.1 / 31.4 ms per C3 step against 30.5 with two): the chip is
-        // busy either way, and a part below two blocks per CU leaves the fixed-point kernel's tail exposed.
-        size_t want = 2;  // GDHIP_KOPT_PARTS: tuning knob
-        if (const char* e = getenv("GDHIP_KOPT_PARTS")) want = (size_t)std::max(1, atoi(e));
-        size_t part = std::max<size_t>((size_t)s_kopt_split_min(), (total + want - 1) / want);
-        // the fixed-point kernel holds one pair per CU (its matrix lives in the CU's registers and LDS): parts of
-        // a whole number of rounds over the 256 CUs leave no extra, mostly empty round (1279 pairs as 640 + 639
-        // are 3 + 3 rounds, as 512 + 767 they are 2 + 3)
-        size_t align = 256;  // GDHIP_KOPT_PART_ALIGN: tuning knob (0: off)
-        if (const char* e = getenv("GDHIP_KOPT_PART_ALIGN")) align = (size_t)std::max(0, atoi(e));
-        if (align > 1 && F == 256 && part > align) part = std::max<size_t>(align, (part + align / 2 - 1) / align * align);
-        return part;
-    }
-    // the FIRST part may be smaller than the others (GDHIP_KOPT_FIRST_PART: tuning knob; 0 = like the others)
-    static size_t first_part_size(size_t part) {
-        if (const char* e = getenv("GDHIP_KOPT_FIRST_PART")) {
-            const size_t f = (size_t)std::max(0, atoi(e));
-            if (f > 0 && f < part) return f;
-        }
-        return part;
-    }
-    static int shear_hold_us() {
-        const char* e = getenv("GDHIP_BATCH_SHEAR_HOLD_US");
-        return e ? atoi(e) : 0;
-    }
-    int join_shear(bool release = false) {
-        // release: the caller is not going to enqueue a first part the chain could wait for (error paths, a call whose only
-        // launch needs the chain).  The staging thread's ordinary join does NOT release: by then the first part is enqueued
-        // and the finisher releases the chain when that part's bandwidths are final.
-        if (release) first_part_done.store(1);
-        std::lock_guard<std::mutex> g(shear_mu);
-        if (shear_joined.load()) return 0;
-        const int e = shear_future.valid() ? shear_future.get() : 0;
-        shear_joined.store(true);
-        mark("shear: joined");
-        return e;
-    }
-    int64_t grid_off = 0;
-    int status_at = 0;
-    int batch_no = 0;
-    std::vector<void*> conv_ctxs;
-    std::vector<int> side_classes;
-    std::vector<int> order;  // grid sizes, largest class (in bytes) first
 
-    // host-side timeline of the call (GDHIP_BATCH_LOG=1 prints it to stderr when the call returns)
-    std::mutex tl_mu;
-    std::vector<std::pair<double, std::string>> tl;
-    bool tl_on = getenv("GDHIP_BATCH_LOG") != nullptr;
-    static double now_ms() {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-    }
+    // Convolution and result copies.
+    struct Conv {
+        int64_t grid_off = 0;
+        int status_at = 0;
+        int batch_no = 0;
+        std::vector<void*> ctxs;
+        std::vector<int> side_classes;
+        std::vector<int> order;           // grid sizes, largest class (in bytes) first
+        std::vector<void*> call_blocks;   // everything to release once the copies have landed
+        // The deferred chain starts only when the FIRST optimiser part's convolution has been enqueued (its stage A, get_h and
+        // first batches get the machine ahead of the chain's 1024-thread blocks; the chain then runs beside the later parts):
+        // same-box A/B, delivered triangle: chain at once 29.4-29.9 ms, released on the first part's bandwidths 28.8-29.5, on
+        // its convolution 28.1-28.9; the stream of triangles 21.7 -> 21.9.  Open at once when the first launch itself needs
+        // the chain, when nothing is staged, and on every error path.
+        Gate first_enqueued;
+        // ... and, for a single delivered call, only when that convolution has RUN: the chain's blocks take every CU for ~3 ms,
+        // and started on the enqueue they ran beside the first part's convolution -- the triangle's first grids, which the 13 ms
+        // of result copies wait for (a timed hold of 1000 / 2000 / 3000 / 4500 us: delivered 26.1 / 24.6 / 24.5 / 24.3 ms, stream
+        // 20.4 / 20.6 / 21.6 / 22.2 against 26.5 / 19.9 without).  The signal is the status word of the first report's last batch:
+        // enqueue_batch pre-sets a batch's words to kStatusPending, the batch's last launch (a copy kernel into page-locked memory)
+        // overwrites them.  A STREAM of calls (settings.results_in_flight) is released on the enqueue: this call's first grids
+        // queue behind the previous call's copies, and the chain beside the first convolution is the better use of the machine
+        // (19.9 against 21.0 ms per triangle).
+        std::atomic<const volatile int32_t*> first_run_word{nullptr};
+        int reports_enqueued = 0;  // (enqueuing thread only)
+    } conv;
+    static constexpr int32_t kStatusPending = 0x7fffffff;
+
+    // Host-side timeline of the call (GDHIP_BATCH_LOG=1 prints it to stderr when the call returns).
+    struct Timeline {
+        std::mutex mu;
+        std::vector<std::pair<double, std::string>> events;
+    } tl;
+    static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     void mark(const char* what, int a = -1, int b = -1) {
-        if (!tl_on) return;
+        if (!env.log) return;
         char buf[160];
         if (a >= 0 && b >= 0)
             snprintf(buf, sizeof buf, "%s (%d, %d)", what, a, b);
@@ -725,14 +915,14 @@ struct Call {
             snprintf(buf, sizeof buf, "%s (%d)", what, a);
         else
             snprintf(buf, sizeof buf, "%s", what);
-        std::lock_guard<std::mutex> g(tl_mu);
-        tl.emplace_back(now_ms(), buf);
+        std::lock_guard<std::mutex> g(tl.mu);
+        tl.events.emplace_back(now_ms(), buf);
     }
     void dump_timeline() {
-        if (!tl_on || tl.empty()) return;
-        std::sort(tl.begin(), tl.end());
+        if (!env.log || tl.events.empty()) return;
+        std::sort(tl.events.begin(), tl.events.end());
         fprintf(stderr, "---- gd_density2d_batch host timeline (ms)\n");
-        for (auto& e : tl) fprintf(stderr, "%9.3f  %s\n", e.first - tl[0].first, e.second.c_str());
+        for (auto& e : tl.events) fprintf(stderr, "%9.3f  %s\n", e.first - tl.events[0].first, e.second.c_str());
     }
 
     std::mutex err_mu;
@@ -755,6 +945,39 @@ struct Call {
         const int rc__ = (call_); \
         if (rc__) return rc__;    \
     } while (0)
+
+    // -- threads.  An exception that escapes a piece of the call's work becomes the call's error and a return code ...
+    template <class Fn>
+    int guarded(const Fn& work) {
+        try {
+            return work();
+        } catch (const std::exception& e) {
+            return fail(GD_ERR_NOMEM, e.what());
+        }
+    }
+    // ... and every thread of the call runs through here: bound to its context, its result always a code, and the gates it
+    // produces (held from this moment, in the starting thread) open with that code when it ends, however it ends.
+    std::future<int> start(void* ctx, std::function<int()> body, Gate* g1 = nullptr, Gate* g2 = nullptr) {
+        return std::async(std::launch::async, [this, ctx, body = std::move(body), o1 = Gate::Opener(g1), o2 = Gate::Opener(g2)]() mutable {
+            Gate::Opener a(std::move(o1)), b(std::move(o2));
+            const int rc = guarded([&] { return ops.bind_thread(ctx), body(); });
+            a.leave(rc), b.leave(rc);
+            return rc;
+        });
+    }
+    int join(Worker& w, const char* what) {
+        bool was_running = false;
+        const int e = w.join(&was_running);
+        if (was_running) mark(what);
+        return e;
+    }
+    int join_binning() { return join(bin.thread, "binning: joined"); }
+    // release: the caller is not going to enqueue a first part the chain could wait for (error paths, a call whose only
+    // launch needs the chain).  The staging thread's ordinary join does NOT release: by then the first part is enqueued.
+    int join_shear(bool release = false) {
+        if (release) conv.first_enqueued.open();
+        return join(shear.thread, "shear: joined");
+    }
 
     double* M(int k) { return meta + (size_t)k * GD_BATCH2D_META; }
 
@@ -800,31 +1023,24 @@ struct Call {
                 return fail(GD_BATCH2D_NEED_NEFF, buf);
             }
         }
-        const std::vector<double>& inv4s2 = lp.inv4s2;
-        const std::vector<int64_t>&maxoffs = lp.maxoffs, &lags = lp.lags;
-        const int ntail = lp.ntail;
-        const int L = (int)lags.size();
+        const int L = (int)lp.lags.size();
         std::vector<double> sums((size_t)m * L);
         mark("neff: probe done");
         // (lag sums the preparation entry has already enqueued for this sample set: nothing to hold back, the binding of
         // kde_lag_sums_batch hands their result over or, on any mismatch, waits for them and launches afresh)
-        if (hold_neff_for_binning && !st.neff_ahead.load()) {
-            const auto t0 = std::chrono::steady_clock::now();
-            while (!bin_launching.load() && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2)) std::this_thread::yield();
-            int hold_us = 120;  // (its launches go out)  GDHIP_BATCH_NEFF_HOLD_US: tuning knob
-            if (const char* e = getenv("GDHIP_BATCH_NEFF_HOLD_US")) hold_us = atoi(e);
-            if (bin_launching.load()) std::this_thread::sleep_for(std::chrono::microseconds(hold_us));
+        if (bin.hold_neff && !st.neff_ahead.load()) {
+            if (bin.launching.wait(0, 2000)) std::this_thread::sleep_for(std::chrono::microseconds(kNeffHoldUs));
             mark("neff: binning chain enqueued");
         }
-        GDB_DEV(h, ops.kde_lag_sums_batch(h, todo.data(), m, inv4s2.data(), lags.data(), L, sums.data()));
+        GDB_DEV(h, ops.kde_lag_sums_batch(h, todo.data(), m, lp.inv4s2.data(), lp.lags.data(), L, sums.data()));
         mark("neff: lag sums done");
         const NeffInput in{N, s.norm, s.sum_w2};
         for (int row = 0; row < m; ++row) {
             const int col = todo[row];
-            const double i4 = inv4s2[row];
+            const double i4 = lp.inv4s2[row];
             auto lag_sum = [&](int64_t k, double* out) -> int { return ops.kde_lag_sums(h, col, i4, &k, 1, out); };
             double v = NAN;
-            const int e = neff_from_lags(in, maxoffs[row], min_corr, &sums[(size_t)row * L], ntail, lag_sum, &v);
+            const int e = neff_from_lags(in, lp.maxoffs[row], min_corr, &sums[(size_t)row * L], lp.ntail, lag_sum, &v);
             if (e) return dev_fail(e, h);
             par[col].neff = v;
         }
@@ -864,59 +1080,47 @@ struct Call {
         return neff_batch(used, false);
     }
 
-    int index_column16(void* ctx, int j, int F, void** out) {
-        const double fw = (bmax[j] - bmin[j]) / (F - 1);
-        IdxCol c;
-        {
-            std::lock_guard<std::mutex> g(st.mu);
-            c = st.idx[std::make_tuple(j, F, 2)];
+    // -- index columns: the stale ones among `cols` for grid size F, with this call's edges
+    int stale_columns(const std::vector<int32_t>& cols, int F, IndexCache::Kind kind, IndexCache::Stale& todo) {
+        std::vector<double> b0, w;
+        for (int j : cols) b0.push_back(bmin[j]), w.push_back((bmax[j] - bmin[j]) / (F - 1));
+        const int rc = cache.stale(pool, cols, F, kind, N, b0.data(), w.data(), todo);
+        return rc ? dev_fail(rc, h) : 0;
+    }
+    // the columns of a class's pairs in order of first appearance: every x then every y, or pair by pair
+    std::vector<int32_t> class_columns(const std::vector<int>& members, bool x_then_y) const {
+        std::vector<int32_t> cols;
+        std::vector<char> seen(n, 0);
+        auto add = [&](int j) {
+            if (!seen[j]) seen[j] = 1, cols.push_back(j);
+        };
+        for (int k : members) {
+            add(ps.jx[k]);
+            if (!x_then_y) add(ps.jy[k]);
         }
-        if (!(c.valid && c.binmin == bmin[j] && c.width == fw)) {
-            if (!c.ptr) {
-                int rc = 0;
-                c.ptr = pool.take(N * 2 + 64, &rc);
-                if (!c.ptr) return dev_fail(rc, h);
-            }
-            GDB_DEV(ctx, ops.prebin(ctx, j, bmin[j], fw, F, c.ptr));
-            c.binmin = bmin[j], c.width = fw, c.valid = true;
-            std::lock_guard<std::mutex> g(st.mu);
-            st.idx[std::make_tuple(j, F, 2)] = c;
-        }
-        *out = c.ptr;
+        if (x_then_y)
+            for (int k : members) add(ps.jy[k]);
+        return cols;
+    }
+    // the u16 index columns of a grid-size class: the stale ones in ONE launch where the library has it (the up-scaled
+    // classes used to cost a launch per column -- 12 launches of 20-70 us between the shear chain and their histograms),
+    // a single one and whatever is left by the single-column entry
+    int index_columns16(void* ctx, const std::vector<int32_t>& cols, int F) {
+        IndexCache::Stale todo;
+        if (ops.prebin_batch) GDB_TRY(stale_columns(cols, F, IndexCache::kU16, todo));
+        if (todo.cols.size() < 2) return 0;
+        GDB_DEV(ctx, ops.prebin_batch(ctx, todo.cols.data(), (int)todo.cols.size(), todo.binmin.data(), todo.width.data(), F, todo.bufs.data()));
+        cache.commit(todo, F, IndexCache::kU16);
         return 0;
     }
-
-    // the stale u16 index columns of a grid-size class in ONE launch (round 6: the up-scaled classes used to cost a launch
-    // per column -- 12 launches of 20-70 us between the shear chain and their histograms)
-    int index_columns16(void* ctx, const std::vector<int>& cols, int F) {
-        if (!ops.prebin_batch) return 0;  // (index_column16 makes them one by one)
-        std::vector<int32_t> todo;
-        std::vector<double> b0, w;
-        std::vector<void*> bufs;
-        for (int j : cols) {
-            const double fw = (bmax[j] - bmin[j]) / (F - 1);
-            IdxCol c;
-            {
-                std::lock_guard<std::mutex> g(st.mu);
-                c = st.idx[std::make_tuple(j, F, 2)];
-            }
-            if (c.valid && c.binmin == bmin[j] && c.width == fw) continue;
-            if (!c.ptr) {
-                int rc = 0;
-                c.ptr = pool.take(N * 2 + 64, &rc);
-                if (!c.ptr) return dev_fail(rc, h);
-                std::lock_guard<std::mutex> g(st.mu);
-                st.idx[std::make_tuple(j, F, 2)] = c;  // (the block is the column's from now on, valid or not)
-            }
-            todo.push_back(j), b0.push_back(bmin[j]), w.push_back(fw), bufs.push_back(c.ptr);
+    int index_column16(void* ctx, int j, int F, void** out) {
+        IndexCache::Stale todo;
+        GDB_TRY(stale_columns({j}, F, IndexCache::kU16, todo));
+        if (!todo.cols.empty()) {
+            GDB_DEV(ctx, ops.prebin(ctx, j, todo.binmin[0], todo.width[0], F, todo.bufs[0]));
+            cache.commit(todo, F, IndexCache::kU16);
         }
-        if (todo.size() < 2) return 0;  // nothing, or one column: the single-column entry serves it
-        GDB_DEV(ctx, ops.prebin_batch(ctx, todo.data(), (int)todo.size(), b0.data(), w.data(), F, bufs.data()));
-        std::lock_guard<std::mutex> g(st.mu);
-        for (size_t q = 0; q < todo.size(); ++q) {
-            IdxCol& c = st.idx[std::make_tuple((int)todo[q], F, 2)];
-            c.binmin = b0[q], c.width = w[q], c.valid = true;
-        }
+        *out = cache.lookup(j, F, IndexCache::kU16);
         return 0;
     }
 
@@ -931,6 +1135,10 @@ struct Call {
             if (classes.at(F).size() > classes.at(best).size()) best = F;
         return best;
     }
+    void publish_hists(int F, void* d) {
+        std::lock_guard<std::mutex> g(enq_mu);
+        hists[F] = d;
+    }
     int binning(void* ctx, int part = 0) {
         const int main_F = main_class();
         for (int F : F_list) {
@@ -939,121 +1147,61 @@ struct Call {
             const int B = (int)members.size();
             int rc = 0;
             if (F == 256 && (unit_weights || byte_index_weights) && B >= kByteIndexMinPairs) {
-                // the base grid of a unit-weight triangle: byte indices, packed 16-bit counters, one block per pair
-                std::vector<int> cols;
-                std::vector<char> seen(n, 0);
-                for (int k : members)
-                    if (!seen[ps.jx[k]]) seen[ps.jx[k]] = 1, cols.push_back(ps.jx[k]);
-                for (int k : members)
-                    if (!seen[ps.jy[k]]) seen[ps.jy[k]] = 1, cols.push_back(ps.jy[k]);
+                // the base grid of a unit-weight triangle: byte indices, packed 16-bit counters, one block per pair;
                 // the stale byte index columns and the histograms over them go out back to back: one wait for both
-                std::vector<int32_t> todo;
-                std::vector<double> b0, w;
-                std::vector<void*> bufs;
-                {
-                    std::lock_guard<std::mutex> g(st.mu);
-                    for (int j : cols) {
-                        const double fw = (bmax[j] - bmin[j]) / 255;
-                        IdxCol& c = st.idx[std::make_tuple(j, 256, 1)];
-                        if (c.valid && c.binmin == bmin[j] && c.width == fw) continue;
-                        todo.push_back(j), b0.push_back(bmin[j]), w.push_back(fw), bufs.push_back(c.ptr);
-                    }
-                }
-                for (size_t q = 0; q < todo.size(); ++q)
-                    if (!bufs[q]) {
-                        bufs[q] = pool.take(N + 64, &rc);
-                        if (!bufs[q]) return dev_fail(rc, h);
-                        std::lock_guard<std::mutex> g(st.mu);
-                        IdxCol& c = st.idx[std::make_tuple((int)todo[q], 256, 1)];
-                        c.ptr = bufs[q], c.valid = false;
-                    }
+                IndexCache::Stale todo;
+                GDB_TRY(stale_columns(class_columns(members, true), 256, IndexCache::kBytes, todo));
                 std::vector<const void*> ix(B), iy(B);
-                {
-                    std::lock_guard<std::mutex> g(st.mu);
-                    for (int q = 0; q < B; ++q) {
-                        ix[q] = st.idx[std::make_tuple((int)ps.jx[members[q]], 256, 1)].ptr;
-                        iy[q] = st.idx[std::make_tuple((int)ps.jy[members[q]], 256, 1)].ptr;
-                    }
+                for (int q = 0; q < B; ++q) {
+                    ix[q] = cache.lookup(ps.jx[members[q]], 256, IndexCache::kBytes);
+                    iy[q] = cache.lookup(ps.jy[members[q]], 256, IndexCache::kBytes);
                 }
-                void* d = pool.take((int64_t)B * 65536 * 8, &rc);
-                if (!d) return dev_fail(rc, h);
-                std::vector<int64_t> bad(todo.size() + 1, 0);
-                mark("binning: prebin8 + hist2d launch", (int)todo.size(), B);
-                bin_launching.store(1);
-                // (two launches: the first optimiser part's rows, then the others -- see bin_future)
-                const int B1 = (F == main_F && bins_first_rows > 0 && bins_first_rows < B) ? bins_first_rows : B;
-                int e = ops.prebin8_hist2d(ctx, todo.data(), (int)todo.size(), b0.data(), w.data(), bufs.data(), bad.data(), B1,
-                                           ix.data(), iy.data(), d);
+                Pool::Lease d{pool, pool.take((int64_t)B * 65536 * 8, &rc)};
+                if (!d.p) return dev_fail(rc, h);
+                const int ntodo = (int)todo.cols.size();
+                std::vector<int64_t> bad(ntodo + 1, 0);
+                mark("binning: prebin8 + hist2d launch", ntodo, B);
+                bin.launching.open();
+                // (two launches: the first optimiser part's rows, then the others -- see Binning)
+                const int B1 = (F == main_F && bin.first_rows > 0 && bin.first_rows < B) ? bin.first_rows : B;
+                int e = ops.prebin8_hist2d(ctx, todo.cols.data(), ntodo, todo.binmin.data(), todo.width.data(), todo.bufs.data(),
+                                           bad.data(), B1, ix.data(), iy.data(), d.p);
                 mark("binning: prebin8 + hist2d done", B1);
-                if (e == 0 || e == GD_ERR_SOLVER) {
-                    std::lock_guard<std::mutex> g(st.mu);
-                    for (size_t q = 0; q < todo.size(); ++q) {
-                        IdxCol& c = st.idx[std::make_tuple((int)todo[q], 256, 1)];
-                        c.binmin = b0[q], c.width = w[q], c.valid = bad[q] == 0;
-                    }
-                }
-                bool published = false;
-                if (e == 0 && B1 < B) {
-                    {
-                        std::lock_guard<std::mutex> g(enq_mu);
-                        hists[F] = d;
-                    }
-                    published = true;
-                    bins_first_done.store(1);
-                    e = ops.hist2d_prebinned8(ctx, B - B1, ix.data() + B1, iy.data() + B1, (char*)d + (int64_t)B1 * 65536 * 8);
+                if (e == 0 || e == GD_ERR_SOLVER) cache.commit(todo, 256, IndexCache::kBytes, bad.data());
+                if (e == 0) {
+                    void* rows = d.keep();  // the class's buffer from here on
+                    publish_hists(F, rows);
+                    if (B1 == B) continue;
+                    bin.first_run.open();
+                    e = ops.hist2d_prebinned8(ctx, B - B1, ix.data() + B1, iy.data() + B1, (char*)rows + (int64_t)B1 * 65536 * 8);
                     mark("binning: the other rows done", B - B1);
                     if (e == 0) continue;
-                }
-                if (e == 0) {
-                    std::lock_guard<std::mutex> g(enq_mu);
-                    hists[F] = d;
-                    continue;
-                }
-                if (published) {  // the first part may be reading its rows: the block lives until the call ends
+                    // the first part may be reading its rows: the block lives until the call ends
                     std::lock_guard<std::mutex> g(enq_mu);
                     hists.erase(F);
-                    bin_stale.push_back(d);
-                } else {
-                    pool.give(d);
+                    bin.stale.push_back(rows);
                 }
                 if (e != GD_ERR_SOLVER) return dev_fail(e, ctx);  // (else: the u16 / u32 path below redoes the class)
             }
-            bin_launching.store(1);  // (this class enqueues as it goes)
-            {
-                std::vector<int> cols;
-                std::vector<char> seen(n, 0);
-                for (int k : members) {
-                    if (!seen[ps.jx[k]]) seen[ps.jx[k]] = 1, cols.push_back(ps.jx[k]);
-                    if (!seen[ps.jy[k]]) seen[ps.jy[k]] = 1, cols.push_back(ps.jy[k]);
-                }
-                GDB_TRY(index_columns16(ctx, cols, F));
-            }
+            bin.launching.open();  // (this class enqueues as it goes)
+            GDB_TRY(index_columns16(ctx, class_columns(members, false), F));
             std::vector<const void*> ix(B), iy(B);
-            for (int q = 0; q < B; ++q) {
-                void* p;
-                GDB_TRY(index_column16(ctx, ps.jx[members[q]], F, &p));
-                ix[q] = p;
-            }
-            for (int q = 0; q < B; ++q) {
-                void* p;
-                GDB_TRY(index_column16(ctx, ps.jy[members[q]], F, &p));
-                iy[q] = p;
-            }
-            void* d = pool.take((int64_t)B * F * F * 8, &rc);
-            if (!d) return dev_fail(rc, h);
-            const int e = ops.hist2d_prebinned(ctx, B, ix.data(), iy.data(), F, d);
+            for (int y = 0; y < 2; ++y)  // (every x column, then every y column)
+                for (int q = 0; q < B; ++q) {
+                    void* p;
+                    GDB_TRY(index_column16(ctx, (y ? ps.jy : ps.jx)[members[q]], F, &p));
+                    (y ? iy : ix)[q] = p;
+                }
+            Pool::Lease d{pool, pool.take((int64_t)B * F * F * 8, &rc)};
+            if (!d.p) return dev_fail(rc, h);
+            const int e = ops.hist2d_prebinned(ctx, B, ix.data(), iy.data(), F, d.p);
             mark("binning: hist2d_prebinned done", B, F);
-            if (e) {
-                pool.give(d);
-                return dev_fail(e, ctx);
-            }
-            std::lock_guard<std::mutex> g(enq_mu);
-            hists[F] = d;
+            if (e) return dev_fail(e, ctx);
+            publish_hists(F, d.keep());
         }
-        bin_launching.store(1);
+        bin.launching.open();
         return 0;
     }
-    // (the thread that runs binning(ctx, 1) sets bins_first_done when binning returns, whatever the route taken)
 
     // -- branch A of getAutoBandwidth2D (mcsamples.py:1347-1378): min/max of the sheared coordinate and the re-binned
     //    base grid of every sheared pair, two batched launches
@@ -1062,7 +1210,7 @@ struct Call {
         shear.A.clear();
         for (int k = 0; k < P; ++k)
             if (plan.branch[k] == 0) shear.A.push_back(k);
-        have_shear = true;
+        shear.have = true;
         const int nA = (int)shear.A.size();
         if (!nA) return 0;
         std::vector<int32_t> ci(nA), cj(nA);
@@ -1117,8 +1265,7 @@ struct Call {
     }
 
     // -- convolution of the pairs of one grid-size class (`only`: mask over the pairs, empty = all) on `force_ctx`, or
-    //    on the stream the two-stream rules pick; `limit_batches` > 0 stops after that many batches and returns the
-    //    remaining ones in `rest` (the caller interleaves classes)
+    //    on the stream the two-stream rules pick
     struct Batch {
         std::vector<int> pos, ks;
     };
@@ -1167,41 +1314,36 @@ struct Call {
             for (int q : b.pos) b.ks.push_back(members[q]);
         return 0;
     }
-    // (GDHIP_BATCH_FIRST_BATCH / GDHIP_BATCH_MAX_BATCH: tuning knobs over the settings' defaults)
-    int s_first_batch() const {
-        if (s.first_batch > 0) return s.first_batch;
-        const char* e = getenv("GDHIP_BATCH_FIRST_BATCH");
-        return e && atoi(e) > 0 ? atoi(e) : 128;
-    }
-    int s_max_batch() const {
-        if (s.max_batch > 0) return s.max_batch;
-        const char* e = getenv("GDHIP_BATCH_MAX_BATCH");
-        return e && atoi(e) > 0 ? atoi(e) : 320;
-    }
+    int s_first_batch() const { return s.first_batch > 0 ? s.first_batch : kFirstBatch; }
+    int s_max_batch() const { return s.max_batch > 0 ? s.max_batch : kMaxBatch; }
     double s_max_batch_bytes() const { return s.max_batch_bytes > 0 ? s.max_batch_bytes : 24e9; }
     int s_two_min() const { return s.two_streams_min > 0 ? s.two_streams_min : 64; }
     int s_two_split() const { return s.two_streams_split > 0 ? s.two_streams_split : 400; }
     int s_kopt_split_min() const { return s.kopt_split_min > 0 ? s.kopt_split_min : 256; }
 
-    bool is_side(int F) const { return std::find(side_classes.begin(), side_classes.end(), F) != side_classes.end(); }
+    bool is_side(int F) const { return std::find(conv.side_classes.begin(), conv.side_classes.end(), F) != conv.side_classes.end(); }
+
+    // (the up-scaled classes' buffers arrive with the deferred chain: null until then)
+    void* class_buffer(int F) {
+        std::lock_guard<std::mutex> g(enq_mu);
+        auto it = hists.find(F);
+        return it == hists.end() ? nullptr : it->second;
+    }
 
     int enqueue_batch(int F, const Batch& b, void* force_ctx) {
         const std::vector<int>& members = classes.at(F);
         void* bctx;
         if (force_ctx)
             bctx = force_ctx;
-        else if (!side_classes.empty() || P > s_two_split())
-            bctx = conv_ctxs[is_side(F) && conv_ctxs.size() > 1 ? 1 : 0];
+        else if (!conv.side_classes.empty() || P > s_two_split())
+            bctx = conv.ctxs[is_side(F) && conv.ctxs.size() > 1 ? 1 : 0];
         else
-            bctx = conv_ctxs[batch_no % conv_ctxs.size()];
-        ++batch_no;
+            bctx = conv.ctxs[conv.batch_no % conv.ctxs.size()];
+        ++conv.batch_no;
         const int B = (int)b.pos.size();
         const int64_t item = (int64_t)F * F * 8;
-        void* d_hist;
-        {
-            std::lock_guard<std::mutex> g(enq_mu);  // (the deferred shear chain may be adding the up-scaled classes' buffers)
-            d_hist = hists.at(F);
-        }
+        void* d_hist = class_buffer(F);  // (under enq_mu: the deferred shear chain may be adding the up-scaled classes' buffers)
+        if (!d_hist) return fail(GD_ERR_BADARG, "a grid-size class has no histograms");
         int rc = 0;
         bool whole = B == (int)members.size();
         for (int q = 0; q < B && whole; ++q) whole = b.pos[q] == q;
@@ -1215,10 +1357,10 @@ struct Call {
         }
         void* d_P = pool.take((int64_t)B * item, &rc);
         if (!d_P) return dev_fail(rc, h);
-        call_blocks.push_back(d_P);
-        int32_t* status = status_pinned + status_at;
-        for (int q = 0; q < B; ++q) status[q] = kStatusPending;  // (overwritten by the batch's last launch: see first_part_flag)
-        if (grid_off + (int64_t)B * F * F > grids_doubles) return fail(GD_ERR_BADARG, "grids_pinned is too small");
+        conv.call_blocks.push_back(d_P);
+        int32_t* status = status_pinned + conv.status_at;
+        for (int q = 0; q < B; ++q) status[q] = kStatusPending;  // (overwritten by the batch's last launch: see Conv::first_run_word)
+        if (conv.grid_off + (int64_t)B * F * F > grids_doubles) return fail(GD_ERR_BADARG, "grids_pinned is too small");
         mark(bctx == h ? "conv: enqueue on main" : "conv: enqueue on twin", B, F);
         GDB_DEV(bctx, ops.density2d_enqueue(bctx, B, F, d_hist, whole ? nullptr : hidx.data(), rxb.data(), ryb.data(), ccb.data(),
                                             wb.data(), fb.data(), s.boundary_correction_order, s.mult_bias_correction_order, d_P,
@@ -1233,15 +1375,15 @@ struct Call {
                 level_status[b.ks[q]] = ls[q];
             }
         }
-        GDB_DEV(bctx, ops.d2h_async(bctx, grids + grid_off, d_P, (int64_t)B * item));
+        GDB_DEV(bctx, ops.d2h_async(bctx, grids + conv.grid_off, d_P, (int64_t)B * item));
         for (int q = 0; q < B; ++q) {
             double* m = M(b.ks[q]);
-            m[1] = (double)(grid_off + (int64_t)q * F * F);
+            m[1] = (double)(conv.grid_off + (int64_t)q * F * F);
             m[29] = bctx == twin ? 1.0 : 0.0;
-            m[30] = (double)(status_at + q);
+            m[30] = (double)(conv.status_at + q);
         }
-        grid_off += (int64_t)B * F * F;
-        status_at += B;
+        conv.grid_off += (int64_t)B * F * F;
+        conv.status_at += B;
         return 0;
     }
 
@@ -1255,7 +1397,7 @@ struct Call {
     // every class, all pairs: classes that go to the second stream are queued there right after the main class's first batch
     int enqueue_all() {
         std::vector<int> main_, side;
-        for (int F : order) (is_side(F) ? side : main_).push_back(F);
+        for (int F : conv.order) (is_side(F) ? side : main_).push_back(F);
         const std::vector<char> all;
         std::vector<Batch> first;
         size_t first_done = 0;
@@ -1277,48 +1419,45 @@ struct Call {
         return 0;
     }
 
-    // -- getAutoBandwidth2D for the batch (mcsamples.py:1325-1419): the optimiser's launches, unit conversions,
-    //    de-rotation of the sheared kernels, fallbacks, widening; on_chunk(ks, index of the launch, number of launches)
-    //    after every launch.
-    //    Sequential mode (`staged` false): every launch is one blocking gd_kopt2d call on the main context.
-    //    Staged mode (large calls with a second and a third stream): the base grid's pairs are cut into parts of about one
-    //    block per CU; the calling thread enqueues stage A of every part (DCT, fixed point, functionals) back to back on the
-    //    main stream, a second thread runs stage B (get_h: the serial TNC minimisations) of part k on the third stream --
-    //    beside stage A of part k + 1 -- and hands the part's final bandwidths to on_chunk, which enqueues its convolution.
-    struct Launch {
-        int F = 0;
-        std::vector<int> ks;   // plan indices in batch order
-        int na = 0;            // leading sheared rows
-        void* d_hist = nullptr;  // class buffer
-        std::vector<int> pos;  // positions within the class buffer of the non-sheared rows
-        bool whole = false;    // the class's buffer as it is
-        // staged mode
-        void* d_batch = nullptr;
-        bool own = false;
-        void* d_rows = nullptr;
-        int32_t ticket = -1;
-        std::vector<double> ne, fb, ci;
-        std::vector<int32_t> dc;
-    };
+    // -- getAutoBandwidth2D for the batch (mcsamples.py:1325-1419): the optimiser's launches (plan_launches), unit
+    //    conversions, de-rotation of the sheared kernels, fallbacks, widening; on_chunk(ks, index of the launch, number of
+    //    launches) after every launch.
+    //    Sequential: every launch is one blocking gd_kopt2d call on the main context.
+    //    Staged (large calls with a second and a third stream): the base grid's pairs are cut into parts; the calling thread
+    //    enqueues stage A of every part (DCT, fixed point, functionals) back to back on the main stream, a second thread runs
+    //    stage B (get_h: the serial TNC minimisations) of part k on the third stream -- beside stage A of part k + 1 -- and a
+    //    third hands the part's final bandwidths to on_chunk, which enqueues its convolution.
     typedef std::function<int(const std::vector<int>&, int, int)> ChunkFn;
+    typedef std::function<int(std::vector<int>, int)> ReportFn;
 
     // a launch that holds sheared rows, or belongs to a class the deferred chain bins, waits for that chain here
-    template <class BufFn>
-    int ready_for(Launch& L, const BufFn& class_buffer) {
-        if (L.na > 0 && L.d_hist && !shear_joined.load() && !getenv("GDHIP_BATCH_SHEAR_JOIN_WHOLE")) {
+    int ready_for(Launch& L) {
+        if (L.na > 0 && L.d_hist && shear.running) {
             // the sheared rows are all this launch is waiting for (its own class has its buffer)
-            while (shear_hist_state.load(std::memory_order_acquire) == 0) std::this_thread::sleep_for(std::chrono::microseconds(20));
+            const bool opened = shear.hists.wait(20, 0);
             mark("shear: histograms awaited");
-            if (shear_hist_state.load(std::memory_order_acquire) == 2) {
-                (void)join_shear();
-                return shear_hist_rc ? shear_hist_rc : GD_ERR_HIP;
+            if (!opened || shear.hists.code()) {
+                const int e = join_shear();
+                return e ? e : GD_ERR_HIP;
             }
         } else if (L.na > 0 || !L.d_hist) {
-            const int e = join_shear();
-            if (e) return e;
+            GDB_TRY(join_shear());
             if (!L.d_hist) L.d_hist = class_buffer(L.F);
             if (!L.d_hist) return fail(GD_ERR_BADARG, "a grid-size class has no histograms");
         }
+        return 0;
+    }
+    // a launch of the base class whose rows the FIRST binning launch has filled may go ahead of the second
+    bool rows_binned_first(const Launch& L) const {
+        if (bin.first_rows <= 0 || L.F != s.fine_bins_2D || L.na > 0 || !L.d_hist) return false;
+        for (int q : L.pos)
+            if (q >= bin.first_rows) return false;
+        return true;
+    }
+    int whole_binning_for(Launch& L) {
+        GDB_TRY(join_binning());
+        if (L.F == s.fine_bins_2D && !L.pos.empty())  // (a class buffer whose second launch failed has been replaced)
+            if (void* p = class_buffer(L.F)) L.d_hist = p;
         return 0;
     }
 
@@ -1397,7 +1536,152 @@ struct Call {
     // which parts' convolutions go to the main stream (behind the optimiser's stage A there): the last two fifths
     static bool part_on_main(int index, int nparts) { return nparts > 1 && index >= nparts - std::max(1, 2 * nparts / 5); }
 
-    int bandwidth_2d(bool staged, void* aux, const ChunkFn& on_chunk) {
+    int run_sequential(std::vector<Launch>& launches, const ReportFn& report) {
+        const int nl = (int)launches.size();
+        int rc = join_binning();
+        for (int q = 0; q < nl && !rc; ++q) {
+            Launch& L = launches[q];
+            const int B = (int)L.ks.size();
+            std::vector<double> out((size_t)B * 12);
+            rc = guarded([&]() -> int {
+                GDB_TRY(whole_binning_for(L));
+                GDB_TRY(ready_for(L));
+                GDB_TRY(build_batch(L));
+                mark("kopt: launch", B, L.F);
+                const int e = ops.kopt2d(h, B, L.F, L.d_batch, L.ne.data(), L.dc.data(), L.fb.data(), L.ci.data(), out.data());
+                mark("kopt: done");
+                return e ? dev_fail(e, h) : 0;
+            });
+            if (L.own) pool.give(L.d_batch);  // (the entry point has waited for its kernels)
+            if (!rc) rc = absorb_rows(L, out);
+            if (!rc) rc = report(L.ks, q);
+        }
+        if (!rc && nl == 0) rc = report({}, 0);
+        return rc;
+    }
+
+    // stage A of every launch from this thread, stage B from a second one, the convolutions from a third
+    int run_staged(std::vector<Launch>& launches, const ReportFn& report) {
+        const int nl = (int)launches.size();
+        std::mutex mu;
+        std::condition_variable cv;
+        int n_staged = 0;
+        bool abort_ = false;
+        // Hand-over of finished parts: the finisher only runs stage B; a third thread enqueues a part's convolution.  When
+        // the finisher did both, the get_h launch of part k + 1 waited for the ~2 ms of host work that enqueueing part k's
+        // ~120 convolution launches takes (trace: stage A of part 2 done at 18.9 ms, its get_h started at 22.9), and the
+        // convolutions of the later parts were launch-bound behind it.
+        std::deque<int> handed;  // parts whose bandwidths are final, in order; -1: no more
+        auto hand = [&](int q) {
+            std::lock_guard<std::mutex> g(mu);
+            handed.push_back(q);
+            cv.notify_all();
+        };
+        Worker enqueuer, finisher;
+        enqueuer.result = start(h, [&]() -> int {
+            int e = 0;
+            for (;;) {
+                int q;
+                {
+                    std::unique_lock<std::mutex> g(mu);
+                    cv.wait(g, [&] { return !handed.empty(); });
+                    q = handed.front();
+                    handed.pop_front();
+                }
+                if (q < 0) return e;
+                if (e) continue;
+                if (part_on_main(q, nl) || !shear.deferred) {
+                    // this part's convolution uses the main context: the staging thread must be done with it.  (The
+                    // earlier parts go to the second context only -- with the deferred shear chain the staging thread
+                    // may still be waiting for that chain when the first part's bandwidths are final, and the first
+                    // part's grids are what the result copies start with.)
+                    std::unique_lock<std::mutex> g(mu);
+                    cv.wait(g, [&] { return n_staged >= nl || abort_; });
+                    if (n_staged < nl) {
+                        e = GD_ERR_HIP;  // (the staging thread gave up: its error is the call's)
+                        continue;
+                    }
+                }
+                e = join_binning();  // (long done by now: a report may convolve any row of the class)
+                if (!e) e = report(launches[q].ks, q);
+                if (conv.reports_enqueued++ == 0 && conv.status_at > 0 && !s.results_in_flight)
+                    conv.first_run_word.store(status_pinned + conv.status_at - 1);  // the last word of the first report's last batch
+                conv.first_enqueued.open();
+            }
+        });
+        finisher.result = start(aux, [&]() -> int {
+            // (whatever ends this thread: the chain is released and the enqueuer learns that no more parts come)
+            const AtExit last{[&] {
+                conv.first_enqueued.open();
+                hand(-1);
+            }};
+            int e = 0;
+            for (int q = 0; q < nl; ++q) {
+                {
+                    std::unique_lock<std::mutex> g(mu);
+                    cv.wait(g, [&] { return n_staged > q || abort_; });
+                    if (n_staged <= q) break;  // (the staging thread gave up)
+                }
+                Launch& L = launches[q];
+                const int B = (int)L.ks.size();
+                std::vector<double> out((size_t)B * 12);
+                if (!e) {
+                    e = guarded([&] { return ops.kopt2d_finish(aux, h, L.ticket, B, L.d_rows, out.data()); });
+                    mark("kopt: part finished", q, B);
+                    if (e) dev_fail(e, aux);
+                } else {
+                    ops.copy_sync(h);  // (never reached in a healthy run: blocks are not freed under running kernels)
+                }
+                // stage B has waited for stage A: the part's input blocks are free
+                if (L.own) pool.give(L.d_batch);
+                pool.give(L.d_rows);
+                if (!e) e = absorb_rows(L, out);
+                if (e) conv.first_enqueued.open();
+                if (!e) hand(q);
+            }
+            return e;
+        });
+        int rc = 0;
+        {
+            // (whatever ends the staging: parts that were never staged are not waited for)
+            const AtExit give_up{[&] {
+                std::lock_guard<std::mutex> g(mu);
+                if (n_staged < nl) abort_ = true;
+                cv.notify_all();
+            }};
+            for (int q = 0; q < nl && !rc; ++q) {
+                Launch& L = launches[q];
+                const int B = (int)L.ks.size();
+                rc = guarded([&]() -> int {
+                    if (!(q == 0 && rows_binned_first(L))) GDB_TRY(whole_binning_for(L));
+                    GDB_TRY(ready_for(L));
+                    GDB_TRY(build_batch(L));
+                    int e = 0;
+                    L.d_rows = pool.take((int64_t)B * GD_KOPT_BLOCK_DOUBLES * 8, &e);
+                    if (!L.d_rows) return dev_fail(e, h);
+                    mark("kopt: stage A enqueue", q, B);
+                    e = ops.kopt2d_enqueue(h, B, L.F, L.d_batch, L.ne.data(), L.dc.data(), L.fb.data(), L.ci.data(), L.d_rows, &L.ticket);
+                    return e ? dev_fail(e, h) : 0;
+                });
+                std::lock_guard<std::mutex> g(mu);
+                if (rc) {
+                    if (L.own && L.d_batch) ops.copy_sync(h), pool.give(L.d_batch);
+                    if (L.d_rows) pool.give(L.d_rows);
+                } else {
+                    ++n_staged;
+                }
+                cv.notify_all();
+            }
+        }
+        mark("kopt: every stage A enqueued");
+        const int e = finisher.join();
+        const int e2 = enqueuer.join();
+        if (!rc) rc = e;
+        if (!rc) rc = e2;
+        return rc;
+    }
+
+    int bandwidth_2d(bool staged, const ChunkFn& on_chunk) {
         const int base_F = s.fine_bins_2D;
         const int m = s.mult_bias_correction_order;
         std::vector<double> widen;
@@ -1406,16 +1690,7 @@ struct Call {
             const double e = 1.0 / 6 - 1.0 / (2 + 4 * (1 + m));
             for (int k = 0; k < P; ++k) widen[k] = 1.1 * py_pow(plan.neff[k], e);
         }
-        if (!have_shear && !shear_deferred) GDB_TRY(shear_histograms(h));
-        std::vector<int> A;  // (= shear.A, which the deferred chain may still be filling)
-        for (int k = 0; k < P; ++k)
-            if (plan.branch[k] == 0) A.push_back(k);
-        const int nA = (int)A.size();
-        auto class_buffer = [&](int F) -> void* {  // (the up-scaled classes' buffers arrive with the deferred chain)
-            std::lock_guard<std::mutex> g(enq_mu);
-            auto it = hists.find(F);
-            return it == hists.end() ? nullptr : it->second;
-        };
+        if (!shear.deferred && !shear.have) GDB_TRY(shear_histograms(h));  // (a deferred chain is still writing `have`)
         std::vector<int> waiting;
         for (int k = 0; k < P; ++k)
             if (plan.branch[k] == 1) {  // rule of thumb (mcsamples.py:1391-1395)
@@ -1424,226 +1699,37 @@ struct Call {
                 W[(size_t)3 * k] = par[ps.jx[k]].sigma_range / d, W[(size_t)3 * k + 1] = par[ps.jy[k]].sigma_range / d, W[(size_t)3 * k + 2] = c;
                 waiting.push_back(k);
             }
-        std::vector<Launch> launches;
-        bool merged = false;
-        for (int F : F_list) {
-            const std::vector<int>& mem = classes.at(F);
-            std::vector<int> pos_C;
-            for (int q = 0; q < (int)mem.size(); ++q)
-                if (plan.branch[mem[q]] == 2) pos_C.push_back(q);
-            if (F == base_F && !pos_C.empty()) {
-                // the sheared pairs ride with the first part of the base grid's own pairs
-                const size_t total = pos_C.size() + (size_t)nA;
-                size_t part = total;
-                if (staged && (int)pos_C.size() >= s_kopt_split_min()) part = base_part_size(total, F);
-                // (deferred shear chain: the sheared rows lead the LAST part instead of the first)
-                const size_t nparts = shear_deferred ? std::max<size_t>(1, (total + part - 1) / part) : 0;
-                for (size_t c0 = 0, first = 1, ip = 0; c0 < pos_C.size(); first = 0, ++ip) {
-                    Launch L;
-                    const bool carries = shear_deferred ? (ip + 1 == nparts || pos_C.size() - c0 <= part) : first != 0;
-                    L.F = F, L.na = carries ? nA : 0, L.d_hist = class_buffer(F);
-                    const size_t part_q = (ip == 0 && nparts > 1) ? first_part_size(part) : part;
-                    size_t take_ = std::min(pos_C.size() - c0, part_q > (size_t)L.na ? part_q - (size_t)L.na : (size_t)1);
-                    if (shear_deferred && carries) take_ = pos_C.size() - c0;  // the last part takes what is left
-                    // (measured, GDHIP_KOPT_FIRST_PART=256: a first part of 256 pairs, the others unchanged -- with the two-launch
-                    // binning delivered 27.2-27.6 against 27.3-27.7 ms, the stream of triangles 21.0-21.2 against 20.6-20.7: the
-                    // result copies saturate PCIe from the first batch on and the copy engine then waits for the second part)
-                    L.pos.assign(pos_C.begin() + c0, pos_C.begin() + c0 + take_);
-                    c0 += take_;
-                    L.whole = L.na == 0 && L.pos.size() == mem.size();
-                    for (int q = 0; q < L.na; ++q) L.ks.push_back(A[q]);
-                    for (int q : L.pos) L.ks.push_back(mem[q]);
-                    launches.push_back(std::move(L));
-                }
-                merged = true;
-                continue;
-            }
-            if (pos_C.empty()) continue;
-            Launch L;
-            L.F = F, L.na = 0, L.d_hist = class_buffer(F), L.pos = pos_C, L.whole = pos_C.size() == mem.size();
-            for (int q : pos_C) L.ks.push_back(mem[q]);
-            launches.push_back(std::move(L));
-        }
-        if (nA && !merged) {
-            GDB_TRY(join_shear(true));
-            Launch L;
-            L.F = base_F, L.na = nA, L.d_hist = shear.d_rot, L.whole = true;
-            L.ks = A;
-            launches.push_back(std::move(L));
-        }
+        std::vector<Launch> launches = plan_launches(plan.branch, F_list, classes, base_F, staged, shear.deferred, s_kopt_split_min());
         const int nl = (int)launches.size();
-        // (the deferred shear chain waits for the first part's bandwidths -- unless that part itself waits for the chain)
-        if (!staged || nl == 0 || launches[0].na > 0 || !launches[0].d_hist) first_part_done.store(1);
-        auto report = [&](std::vector<int> ks, int index) -> int {
+        for (Launch& L : launches) {
+            if (L.pos.empty()) {  // the sheared pairs alone: their histograms are the buffer
+                GDB_TRY(join_shear(true));
+                L.d_hist = shear.d_rot;
+            } else {
+                L.d_hist = class_buffer(L.F);
+            }
+        }
+        // (the deferred shear chain waits for the first part's convolution -- unless that part itself waits for the chain)
+        if (!staged || nl == 0 || launches[0].na > 0 || !launches[0].d_hist) conv.first_enqueued.open();
+        ReportFn report = [&](std::vector<int> ks, int index) -> int {
             if (!waiting.empty()) {
                 // the rule-of-thumb pairs ride with the first report -- except, with the deferred shear chain, those of a
                 // class that chain bins (an up-scaled grid): they wait for the last report, when the chain has been joined
                 std::vector<int> all, later;
-                for (int k : waiting) ((shear_deferred && ps.F[k] != base_F && index + 1 < nl) ? later : all).push_back(k);
+                for (int k : waiting) ((shear.deferred && ps.F[k] != base_F && index + 1 < nl) ? later : all).push_back(k);
                 all.insert(all.end(), ks.begin(), ks.end());
                 ks.swap(all);
                 waiting.swap(later);
             }
             if (m)
                 for (int k : ks) W[(size_t)3 * k] *= widen[k], W[(size_t)3 * k + 1] *= widen[k];
-            if (shear_deferred && index + 1 >= nl) {
-                // the last report convolves the rule-of-thumb pairs of the classes the chain bins: the WHOLE chain, not only
-                // its sheared histograms (ready_for), has to be through
-                const int e = join_shear();
-                if (e) return e;
-            }
+            // the last report convolves the rule-of-thumb pairs of the classes the chain bins: the WHOLE chain, not only
+            // its sheared histograms (ready_for), has to be through
+            if (shear.deferred && index + 1 >= nl) GDB_TRY(join_shear());
             if (!ks.empty() || index + 1 >= nl) return on_chunk(ks, index, nl);
             return 0;
         };
-        int rc = 0;
-        // a launch of the base class whose rows the FIRST binning launch has filled may go ahead of the second
-        auto rows_binned_first = [&](const Launch& L) {
-            if (bins_first_rows <= 0 || L.F != base_F || L.na > 0 || !L.d_hist) return false;
-            for (int q : L.pos)
-                if (q >= bins_first_rows) return false;
-            return true;
-        };
-        auto whole_binning_for = [&](Launch& L) -> int {
-            const int e = join_binning();
-            if (e) return e;
-            if (L.F == base_F && !L.pos.empty())  // (a class buffer whose second launch failed has been replaced)
-                if (void* p = class_buffer(L.F)) L.d_hist = p;
-            return 0;
-        };
-        if (!staged || nl == 0) {
-            rc = join_binning();
-            for (int q = 0; q < nl && !rc; ++q) {
-                Launch& L = launches[q];
-                const int B = (int)L.ks.size();
-                rc = whole_binning_for(L);
-                if (!rc) rc = ready_for(L, class_buffer);
-                if (!rc) rc = build_batch(L);
-                std::vector<double> out((size_t)B * 12);
-                if (!rc) {
-                    mark("kopt: launch", B, L.F);
-                    rc = ops.kopt2d(h, B, L.F, L.d_batch, L.ne.data(), L.dc.data(), L.fb.data(), L.ci.data(), out.data());
-                    mark("kopt: done");
-                    if (rc) dev_fail(rc, h);
-                }
-                if (L.own) pool.give(L.d_batch);  // (the entry point has waited for its kernels)
-                if (!rc) rc = absorb_rows(L, out);
-                if (!rc) rc = report(L.ks, q);
-            }
-            if (!rc && nl == 0) rc = report({}, 0);
-        } else {
-            // ---- staged: stage A of every launch from this thread, stage B + the hand-over from a second one
-            std::mutex mu;
-            std::condition_variable cv;
-            int n_staged = 0;
-            bool abort_ = false;
-            // Hand-over of finished parts (round 5): the finisher only runs stage B; a third thread enqueues a part's
-            // convolution.  When the finisher did both, the get_h launch of part k + 1 waited for the ~2 ms of host work
-            // that enqueueing part k's ~120 convolution launches takes (trace: stage A of part 2 done at 18.9 ms, its get_h
-            // started at 22.9), and the convolutions of the later parts were launch-bound behind it.
-            std::deque<int> handed;  // parts whose bandwidths are final, in order; -1: no more
-            std::future<int> enqueuer = std::async(std::launch::async, [&]() -> int {
-                ops.bind_thread(h);
-                int e = 0;
-                for (;;) {
-                    int q;
-                    {
-                        std::unique_lock<std::mutex> g(mu);
-                        cv.wait(g, [&] { return !handed.empty(); });
-                        q = handed.front();
-                        handed.pop_front();
-                    }
-                    if (q < 0) return e;
-                    if (e) continue;
-                    if (part_on_main(q, nl) || !shear_deferred) {
-                        // this part's convolution uses the main context: the staging thread must be done with it.  (The
-                        // earlier parts go to the second context only -- with the deferred shear chain the staging thread
-                        // may still be waiting for that chain when the first part's bandwidths are final, and the first
-                        // part's grids are what the result copies start with.)
-                        std::unique_lock<std::mutex> g(mu);
-                        cv.wait(g, [&] { return n_staged >= nl || abort_; });
-                        if (n_staged < nl) {
-                            e = GD_ERR_HIP;  // (the staging thread gave up: its error is the call's)
-                            continue;
-                        }
-                    }
-                    e = join_binning();  // (long done by now: a report may convolve any row of the class)
-                    if (!e) e = report(launches[q].ks, q);
-                    if (reports_enqueued++ == 0 && status_at > 0 && !s.results_in_flight && !getenv("GDHIP_BATCH_SHEAR_ON_ENQUEUE"))
-                        first_part_flag.store(status_pinned + status_at - 1);  // the last word of the first report's last batch
-                    first_part_done.store(1);  // the first part's convolution is enqueued: the deferred shear chain may start
-                }
-            });
-            std::future<int> finisher = std::async(std::launch::async, [&]() -> int {
-                ops.bind_thread(aux);
-                int e = 0;
-                auto hand = [&](int q) {
-                    std::lock_guard<std::mutex> g(mu);
-                    handed.push_back(q);
-                    cv.notify_all();
-                };
-                for (int q = 0; q < nl; ++q) {
-                    {
-                        std::unique_lock<std::mutex> g(mu);
-                        cv.wait(g, [&] { return n_staged > q || abort_; });
-                        if (n_staged <= q) break;  // (the staging thread gave up)
-                    }
-                    Launch& L = launches[q];
-                    const int B = (int)L.ks.size();
-                    std::vector<double> out((size_t)B * 12);
-                    if (!e) {
-                        e = ops.kopt2d_finish(aux, h, L.ticket, B, L.d_rows, out.data());
-                        mark("kopt: part finished", q, B);
-                        if (e) dev_fail(e, aux);
-                    } else {
-                        ops.copy_sync(h);  // (never reached in a healthy run: blocks are not freed under running kernels)
-                    }
-                    // stage B has waited for stage A: the part's input blocks are free
-                    if (L.own) pool.give(L.d_batch);
-                    pool.give(L.d_rows);
-                    if (!e) e = absorb_rows(L, out);
-                    if (e || getenv("GDHIP_BATCH_SHEAR_AFTER_GET_H")) first_part_done.store(1);  // (A/B: release on the bandwidths already)
-                    if (!e) hand(q);
-                }
-                first_part_done.store(1);
-                hand(-1);
-                return e;
-            });
-            for (int q = 0; q < nl && !rc; ++q) {
-                Launch& L = launches[q];
-                const int B = (int)L.ks.size();
-                if (!(q == 0 && rows_binned_first(L))) rc = whole_binning_for(L);
-                if (!rc) rc = ready_for(L, class_buffer);
-                if (!rc) rc = build_batch(L);
-                if (!rc) {
-                    L.d_rows = pool.take((int64_t)B * GD_KOPT_BLOCK_DOUBLES * 8, &rc);
-                    if (!L.d_rows) dev_fail(rc, h);
-                }
-                if (!rc) {
-                    mark("kopt: stage A enqueue", q, B);
-                    rc = ops.kopt2d_enqueue(h, B, L.F, L.d_batch, L.ne.data(), L.dc.data(), L.fb.data(), L.ci.data(), L.d_rows, &L.ticket);
-                    if (rc) dev_fail(rc, h);
-                }
-                std::lock_guard<std::mutex> g(mu);
-                if (rc) {
-                    abort_ = true;
-                    if (L.own && L.d_batch) ops.copy_sync(h), pool.give(L.d_batch);
-                    if (L.d_rows) pool.give(L.d_rows);
-                } else {
-                    ++n_staged;
-                }
-                cv.notify_all();
-            }
-            {
-                std::lock_guard<std::mutex> g(mu);
-                if (n_staged < nl) abort_ = true;
-                cv.notify_all();
-            }
-            mark("kopt: every stage A enqueued");
-            const int e = finisher.get();
-            const int e2 = enqueuer.get();
-            if (!rc) rc = e;
-            if (!rc) rc = e2;
-        }
+        int rc = (!staged || nl == 0) ? run_sequential(launches, report) : run_staged(launches, report);
         {
             const int e0 = join_binning();
             const int e = join_shear(true);  // (an error path may get here before any launch asked for it)
@@ -1654,7 +1740,92 @@ struct Call {
         return rc;
     }
 
+    // -- the O(N) phase of a large call.  Three streams are busy from the start: the N_eff kernels (fp64 exp-bound) on the
+    //    main context, the byte-index binning (LDS atomics) on the second, the sheared min/max + re-binning (HBM-bound) on
+    //    a third the library creates for itself; the per-pair scalars and the branch plan are worked out meanwhile.
+    void start_neff_thread() {
+        bin.hold_neff = unit_weights;
+        neff.result = start(h, [this] { return neff_batch(used, true); });
+    }
+    // the deferred chain (see Shear): large unit-weight calls; it needs the fourth context
+    void choose_shear_mode() {
+        shear.deferred = env.shear_deferred && unit_weights && P >= env.shear_deferred_min;
+        // (measured: the chain's stream at the LOWEST priority, so that the optimiser's blocks would be dispatched ahead of it
+        // -- 30.0-30.4 ms per delivered triangle against 29.5-29.7 with the high priority create_aux gives it, 30.6-30.8 with
+        // the chain joined in front of the optimiser: its 1024-thread blocks hold their CUs either way, and a low priority
+        // only delays the chain's end)
+        if (shear.deferred && !st.aux2 && ops.create_aux(h, &st.aux2)) {
+            if (st.aux2) ops.destroy_aux(st.aux2), st.aux2 = nullptr;
+            shear.deferred = false, (void)ops.last_error(h);
+        }
+    }
+    // the rows of the main class that the first binning launch fills: the first optimiser part's (see Binning)
+    void plan_first_binning_rows() {
+        const bool will_stage = aux != nullptr && !s.want_levels && P >= s_two_min() && P > s_two_split() && !s.bandwidths_only;
+        if (!(shear.deferred && will_stage && s.fine_bins_2D == 256 && main_class() == 256 && !env.one_binning)) return;
+        std::vector<int>& mem = classes[256];
+        std::stable_partition(mem.begin(), mem.end(), [&](int k) { return plan.branch[k] == 2; });
+        size_t nC = 0, nA = 0;
+        for (int k : mem) nC += plan.branch[k] == 2;
+        for (int k = 0; k < P; ++k) nA += plan.branch[k] == 0;
+        if ((int)nC < s_kopt_split_min()) return;
+        // (measured: a first part of 256 pairs, the others unchanged -- delivered 27.2-27.6 against 27.3-27.7 ms, the stream of
+        // triangles 21.0-21.2 against 20.6-20.7: the result copies saturate PCIe from the first batch on and the copy engine
+        // then waits for the second part.  So the first part is a part like the others.)
+        const size_t part = base_part_size(nC + nA, 256, s_kopt_split_min()), first = std::min(nC, part);
+        if (nC + nA > part && first < mem.size()) bin.first_rows = (int)first;
+    }
+    void start_binning_thread(bool split_classes) {
+        bin.thread.result = start(twin, [this, split_classes] { return binning(twin, split_classes ? 1 : 0); }, &bin.first_run, &bin.done);
+    }
+    // What the deferred chain holds for before it takes the machine: the whole main binning has run, the first optimiser
+    // part's convolution is enqueued and -- where that is the signal (Conv::first_run_word) -- has run.  Every wait is bounded.
+    void hold_chain_start() {
+        bin.done.wait(50, 50000);
+        conv.first_enqueued.wait(50, 20000);
+        if (const volatile int32_t* word = conv.first_run_word.load())
+            poll_until([word] { return *word != kStatusPending; }, 20, 20000);
+        mark("shear: main binning has run, first part's bandwidths final");
+    }
+    void start_shear_chain(bool split_classes) {
+        void* sctx = shear.deferred ? st.aux2 : aux;
+        shear.thread.result = start(sctx, [this, sctx, split_classes] {
+            if (shear.deferred) hold_chain_start();
+            const int e = shear_histograms(sctx);
+            shear.hists.open(e);
+            if (env.side_binning_delay_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(env.side_binning_delay_ms));
+            const int e2 = split_classes ? binning(sctx, 2) : 0;  // the up-scaled classes, behind the shear chain
+            return e ? e : e2;
+        }, &shear.hists);
+    }
+    // N_eff, the plan's second half, the chain (unless deferred) and the binning -- of the first optimiser part's rows only
+    // where the main class is binned in two launches: whoever needs more joins the binning (bandwidth_2d)
+    int join_linear_phase(int rc, bool* exchanged) {
+        int e = neff.join();
+        if (!rc) rc = e;
+        if (!rc) rc = neff_complete(exchanged);  // (multi-rank: the other ranks' values, from this thread)
+        if (!rc) fill_plan(par, ps, plan, s.pair_neff);
+        if (shear.deferred) {
+            shear.running = shear.thread.result.valid();  // joined by the first launch that needs it
+        } else {
+            e = join_shear();
+            if (!rc) rc = e;
+        }
+        if (bin.first_rows > 0 && !rc && bin.first_run.wait(20, 0) && bin.first_run.code() == 0) {
+            mark("binning: first part's rows done", bin.first_rows);
+        } else {
+            e = join_binning();
+            if (!rc) rc = e;
+        }
+        if (rc) (void)join_shear(true);
+        return rc;
+    }
+
     int run(int32_t* tokens_out2) {
+        const int rc = guarded([&] { return run_steps(tokens_out2); });
+        return rc ? cleanup(rc) : 0;
+    }
+    int run_steps(int32_t* tokens_out2) {
         tokens_out2[0] = tokens_out2[1] = -1;
         const int base_F = s.fine_bins_2D, bco = s.boundary_correction_order;
         const double ss = s.smooth_scale_2D;
@@ -1673,7 +1844,7 @@ struct Call {
         int32_t hw = 0;
         GDB_DEV(h, ops.weights_kind(h, &hw));
         unit_weights = hw == 0;
-        byte_index_weights = hw == 2 && !getenv("GDHIP_NO_WSORT");
+        byte_index_weights = hw == 2 && !env.no_wsort;
         for (int k = 0; k < P; ++k)
             if (pairs[2 * k] < 0 || pairs[2 * k] >= n || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= n)
                 return fail(GD_ERR_BADARG, "pair index out of range");
@@ -1689,23 +1860,12 @@ struct Call {
         bool need_neff = false;
         if (auto_bw && !s.pair_neff)
             for (int j : used) need_neff = need_neff || isnan(par[j].neff);
-        // Large calls keep three streams busy from the start: the N_eff kernels (fp64 exp-bound) on the main context, the
-        // byte-index binning (LDS atomics) on the second, the sheared min/max + re-binning (HBM-bound) on a third the
-        // library creates for itself; the per-pair scalars and the branch plan are worked out here meanwhile.
-        void* aux = nullptr;
-        const bool overlap = auto_bw && P >= 64 && twin != nullptr;
+        const bool overlap = auto_bw && P >= 64 && twin != nullptr;  // a large call: see start_neff_thread
         if (overlap) {
             if (!st.aux) GDB_DEV(h, ops.create_aux(h, &st.aux));
             aux = st.aux;
+            if (need_neff) start_neff_thread();
         }
-        std::future<int> neff_f, shear_f;
-        bin_launching.store(0);
-        hold_neff_for_binning = overlap && need_neff && unit_weights && !getenv("GDHIP_BATCH_NO_NEFF_HOLD");
-        if (overlap && need_neff)
-            neff_f = std::async(std::launch::async, [this] {
-                ops.bind_thread(h);
-                return neff_batch(used, true);
-            });
         bmin.assign(n, NAN), bmax.assign(n, NAN);
         for (int j : used) bin_edges(par[j], &bmin[j], &bmax[j]);
         pair_scalars(s, n, corrmat, pairs, P, ps);
@@ -1724,128 +1884,32 @@ struct Call {
         int64_t need = 0;
         for (int k = 0; k < P; ++k) need += (int64_t)ps.F[k] * ps.F[k];
         if (need > grids_doubles && !s.bandwidths_only) {
-            if (neff_f.valid()) neff_f.get();
+            (void)neff.join();
             return fail(GD_ERR_BADARG, "grids_pinned is too small");
         }
         std::vector<double> rngx(P), rngy(P);
         for (int k = 0; k < P; ++k) rngx[k] = bmax[ps.jx[k]] - bmin[ps.jx[k]], rngy[k] = bmax[ps.jy[k]] - bmin[ps.jy[k]];
         int rc = 0;
-        if (auto_bw) {
-            if (overlap) {
-                const bool split_classes = F_list.size() > 1;
-                bin_done.store(0);
-                first_part_done.store(0);
-                first_part_flag.store(nullptr), reports_enqueued = 0;
-                {
-                    // deferred shear chain (see shear_future): large unit-weight calls whose main class takes the byte-index
-                    // route; GDHIP_BATCH_SHEAR_DEFERRED=0 restores the join in front of the optimiser
-                    const char* e = getenv("GDHIP_BATCH_SHEAR_DEFERRED");
-                    const char* emin = getenv("GDHIP_BATCH_SHEAR_DEFERRED_MIN");  // (tests lower it)
-                    shear_deferred = (e ? atoi(e) != 0 : true) && unit_weights && P >= (emin ? atoi(emin) : 256);
-                    if (shear_deferred && !st.aux2) {
-                        // (measured: the chain's stream at the LOWEST priority, so that the optimiser's blocks would be
-                        // dispatched ahead of it -- 30.0-30.4 ms per delivered triangle against 29.5-29.7 with the high
-                        // priority create_aux gives it, 30.6-30.8 with the chain joined in front of the optimiser: its
-                        // 1024-thread blocks hold their CUs either way, and a low priority only delays the chain's end)
-                        int rc2 = ops.create_aux(h, &st.aux2);
-                        if (!rc2 && ops.stream_priority && getenv("GDHIP_BATCH_SHEAR_LOW_PRIORITY")) rc2 = ops.stream_priority(st.aux2, -1);
-                        if (rc2) {
-                            if (st.aux2) ops.destroy_aux(st.aux2), st.aux2 = nullptr;
-                            shear_deferred = false, (void)ops.last_error(h);
-                        }
-                    }
-                    shear_after_binning = shear_deferred;
-                }
-                // (the branch plan needs the limits and the covariance only)
-                rc = make_plan(s, par, n, cov, ps, rngx, rngy, 0.2, plan, err);
-                bins_first_rows = 0;
-                bins_first_done.store(0);
-                const bool will_stage = aux != nullptr && !s.want_levels && P >= s_two_min() && P > s_two_split() && !s.bandwidths_only;
-                if (!rc && shear_deferred && will_stage && base_F == 256 && main_class() == 256 && !getenv("GDHIP_BATCH_ONE_BINNING")) {
-                    std::vector<int>& mem = classes[256];
-                    std::stable_partition(mem.begin(), mem.end(), [&](int k) { return plan.branch[k] == 2; });
-                    size_t nC = 0, nA = 0;
-                    for (int k : mem) nC += plan.branch[k] == 2;
-                    for (int k = 0; k < P; ++k) nA += plan.branch[k] == 0;
-                    if ((int)nC >= s_kopt_split_min()) {
-                        const size_t part = base_part_size(nC + nA, 256), first = std::min(nC, first_part_size(part));
-                        if (nC + nA > part && first < mem.size()) bins_first_rows = (int)first;
-                    }
-                }
-                bin_joined = false, bin_rc = 0;
-                bin_future = std::async(std::launch::async, [this, split_classes] {
-                                 ops.bind_thread(twin);
-                                 const int e = binning(twin, split_classes ? 1 : 0);
-                                 bins_first_done.store(1);
-                                 bin_done.store(1);
-                                 return e;
-                             }).share();
-                if (!rc) shear_hist_state.store(0);
-                if (!rc)  // the shear chain starts at once
-                    shear_f = std::async(std::launch::async, [this, aux, split_classes] {
-                        void* sctx = shear_deferred ? st.aux2 : aux;
-                        ops.bind_thread(sctx);
-                        if (shear_after_binning) {
-                            const auto t0 = std::chrono::steady_clock::now();
-                            while (!bin_done.load() && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(50))
-                                std::this_thread::sleep_for(std::chrono::microseconds(50));
-                            if (!getenv("GDHIP_BATCH_SHEAR_AT_ONCE")) {
-                                const auto t1 = std::chrono::steady_clock::now();
-                                while (!first_part_done.load() && std::chrono::steady_clock::now() - t1 < std::chrono::milliseconds(20))
-                                    std::this_thread::sleep_for(std::chrono::microseconds(50));
-                            }
-                            // (GDHIP_BATCH_SHEAR_HOLD_US: the chain's start held back further -- tuning knob)
-                            if (const volatile int32_t* flag = first_part_flag.load()) {  // ... and has run (first_part_flag)
-                                const auto t2 = std::chrono::steady_clock::now();
-                                while (*flag == kStatusPending && std::chrono::steady_clock::now() - t2 < std::chrono::milliseconds(20))
-                                    std::this_thread::sleep_for(std::chrono::microseconds(20));
-                            }
-                            if (first_part_done.load() && shear_hold_us() > 0)
-                                std::this_thread::sleep_for(std::chrono::microseconds(shear_hold_us()));
-                            mark("shear: main binning has run, first part's bandwidths final");
-                        }
-                        const int e = shear_histograms(sctx);
-                        shear_hist_rc = e;
-                        shear_hist_state.store(e ? 2 : 1, std::memory_order_release);
-                        if (const char* d = getenv("GDHIP_BATCH_TEST_SIDE_BINNING_DELAY_MS"))  // test hook: a slow second half
-                            std::this_thread::sleep_for(std::chrono::milliseconds(atoi(d)));
-                        const int e2 = split_classes ? binning(sctx, 2) : 0;  // the up-scaled classes, behind the shear chain
-                        return e ? e : e2;
-                    });  // (no plan: the call fails; the side classes are not needed)
-                int e = neff_f.valid() ? neff_f.get() : 0;
-                if (!rc) rc = e;
-                if (!rc) rc = neff_complete(&exchanged);  // (multi-rank: the other ranks' values, from this thread)
-                if (!rc) fill_plan(par, ps, plan, s.pair_neff);
-                if (shear_f.valid()) {
-                    if (shear_deferred) {
-                        shear_future = std::move(shear_f), shear_joined.store(false);  // joined by the first launch that needs it
-                    } else {
-                        e = shear_f.get();
-                        if (!rc) rc = e;
-                    }
-                }
-                if (bins_first_rows > 0 && !rc) {
-                    // the first optimiser part's rows only; whoever needs more joins the binning (bandwidth_2d)
-                    while (!bins_first_done.load()) std::this_thread::sleep_for(std::chrono::microseconds(20));
-                    mark("binning: first part's rows done", bins_first_rows);
-                } else {
-                    e = join_binning();
-                    if (!rc) rc = e;
-                }
-                if (rc) (void)join_shear(true);
-            } else {
-                rc = s.pair_neff ? 0 : neff_batch(used, true);
-                if (!rc) rc = neff_complete(&exchanged);
-                if (!rc) rc = binning(h);
-                if (!rc) rc = make_plan(s, par, n, cov, ps, rngx, rngy, 0.2, plan, err);
-                if (!rc) fill_plan(par, ps, plan, s.pair_neff);
-            }
+        if (auto_bw && overlap) {
+            const bool split_classes = F_list.size() > 1;
+            choose_shear_mode();
+            rc = make_plan(s, par, n, cov, ps, rngx, rngy, 0.2, plan, err);  // (needs the limits and the covariance only)
+            if (!rc) plan_first_binning_rows();
+            start_binning_thread(split_classes);
+            if (!rc) start_shear_chain(split_classes);  // (no plan: the call fails; the side classes are not needed)
+            rc = join_linear_phase(rc, &exchanged);
+        } else if (auto_bw) {
+            rc = s.pair_neff ? 0 : neff_batch(used, true);
+            if (!rc) rc = neff_complete(&exchanged);
+            if (!rc) rc = binning(h);
+            if (!rc) rc = make_plan(s, par, n, cov, ps, rngx, rngy, 0.2, plan, err);
+            if (!rc) fill_plan(par, ps, plan, s.pair_neff);
         } else {
             rc = neff_exchange(&exchanged);  // the collective is unconditional: once per call on every rank
             if (!rc && !s.bandwidths_only) rc = binning(h);
         }
         mark("binning / N_eff / plan joined");
-        if (rc) return cleanup(rc);
+        if (rc) return rc;
         // ---- convolution set-up: flag bits (mcsamples.py:1688-1703, 1794): bits 0/1 = x bot/top, 2/3 = y bot/top,
         //      4/5 = x/y periodic, 6 = has_prior
         flags.resize(P), group.resize(P);
@@ -1859,24 +1923,24 @@ struct Call {
         }
         rx.assign(P, NAN), ry.assign(P, NAN), cc.assign(P, NAN), smooth.assign(P, NAN), winw.assign(P, 0), W.assign((size_t)3 * P, NAN);
         const bool lazy = !s.want_levels;
-        conv_ctxs = {h};
+        conv.ctxs = {h};
         if (lazy && twin && P >= s_two_min()) {
             if (P > s_two_split()) {
                 for (int F : F_list)
-                    if ((int)classes.at(F).size() < 64) side_classes.push_back(F);
-                if (side_classes.size() == F_list.size()) side_classes.clear();
+                    if ((int)classes.at(F).size() < 64) conv.side_classes.push_back(F);
+                if (conv.side_classes.size() == F_list.size()) conv.side_classes.clear();
             }
-            conv_ctxs.push_back(twin);
+            conv.ctxs.push_back(twin);
         }
         // largest class (in bytes) first: the copy of the last, smallest one is the only exposed one
-        order = F_list;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        conv.order = F_list;
+        std::stable_sort(conv.order.begin(), conv.order.end(), [&](int a, int b) {
             return (int64_t)classes.at(a).size() * a * a > (int64_t)classes.at(b).size() * b * b;
         });
         std::vector<int> all_k(P);
         for (int k = 0; k < P; ++k) all_k[k] = k;
         if (auto_bw) {
-            const bool staged = aux != nullptr && conv_ctxs.size() > 1 && P > s_two_split() && !s.bandwidths_only;
+            const bool staged = aux != nullptr && conv.ctxs.size() > 1 && P > s_two_split() && !s.bandwidths_only;
             if (staged) {
                 // every part's convolution is enqueued (by the thread that finishes the parts) as soon as its bandwidths are
                 // final: the first parts on the second stream, beside the optimiser's stage A of the later parts on the
@@ -1888,16 +1952,16 @@ struct Call {
                     const bool to_main = part_on_main(index, nparts);
                     // (measured alternatives, C3 step: every part on the second stream 31.4 ms, the last parts on the third
                     // -- high-priority -- stream 36.3 ms, against 30.4 ms as below)
-                    for (int F : order) {
-                        void* target = (is_side(F) || !to_main) ? conv_ctxs[1] : conv_ctxs[0];
+                    for (int F : conv.order) {
+                        void* target = (is_side(F) || !to_main) ? conv.ctxs[1] : conv.ctxs[0];
                         GDB_TRY(run_class(F, only, target));
                     }
                     return 0;
                 };
-                rc = bandwidth_2d(true, aux, on_chunk);
+                rc = bandwidth_2d(true, on_chunk);
             } else {
                 ChunkFn on_chunk = [&](const std::vector<int>&, int, int) -> int { return 0; };
-                rc = bandwidth_2d(false, nullptr, on_chunk);
+                rc = bandwidth_2d(false, on_chunk);
                 if (!rc) {
                     set_scales(all_k);
                     if (!s.bandwidths_only) rc = enqueue_all();
@@ -1929,30 +1993,27 @@ struct Call {
             }
             if (!s.bandwidths_only) rc = enqueue_all();
         }
-        if (rc) return cleanup(rc);
+        if (rc) return rc;
         for (int k = 0; k < P; ++k) {
             double* m = M(k);
             m[18] = rx[k], m[19] = ry[k], m[20] = cc[k], m[21] = (double)winw[k], m[22] = ps.warn[k];
         }
         mark("all batches enqueued");
-        for (auto& kv : hists) call_blocks.push_back(kv.second);
-        hists.clear();
-        for (void* p : bin_stale) call_blocks.push_back(p);
-        bin_stale.clear();
+        class_buffers_to_call_blocks();
         GDB_DEV(h, ops.copy_mark(h, &tokens_out2[0]));
-        if (conv_ctxs.size() > 1) GDB_DEV(twin, ops.copy_mark(twin, &tokens_out2[1]));
+        if (conv.ctxs.size() > 1) GDB_DEV(twin, ops.copy_mark(twin, &tokens_out2[1]));
         if (!lazy) {
-            for (void* c : conv_ctxs) GDB_DEV(c, ops.copy_sync(c));
-            for (void* p : call_blocks) pool.give(p);
-            call_blocks.clear();
+            for (void* c : conv.ctxs) GDB_DEV(c, ops.copy_sync(c));
+            for (void* p : conv.call_blocks) pool.give(p);
+            conv.call_blocks.clear();
             return 0;
         }
         // This call's blocks wait for its copies.  The previous call's copies are ahead of this call's on the copy
         // streams: completing it here costs no waiting, and its device blocks return to the pool even if nobody ever
         // read its grids.
         Pending cur;
-        cur.blocks.swap(call_blocks);
-        cur.tok_main = tokens_out2[0], cur.tok_twin = tokens_out2[1], cur.twin = conv_ctxs.size() > 1 ? twin : nullptr;
+        cur.blocks.swap(conv.call_blocks);
+        cur.tok_main = tokens_out2[0], cur.tok_twin = tokens_out2[1], cur.twin = conv.ctxs.size() > 1 ? twin : nullptr;
         cur.live = true;
         const int e_prev = complete_pending(st, ops, h, st.prev);
         st.prev = std::move(cur);
@@ -1962,19 +2023,23 @@ struct Call {
         return 0;
     }
 
+    void class_buffers_to_call_blocks() {  // (released with the call's other blocks)
+        for (auto& kv : hists) conv.call_blocks.push_back(kv.second);
+        hists.clear();
+        conv.call_blocks.insert(conv.call_blocks.end(), bin.stale.begin(), bin.stale.end());
+        bin.stale.clear();
+    }
     // an error after device work was started: wait for whatever is in flight, hand every block back
     int cleanup(int rc) {
+        (void)neff.join();
         (void)join_binning();
         (void)join_shear(true);  // (a deferred chain still running on its own context uses the pool and the class table)
         ops.copy_sync(h);
         if (twin) ops.copy_sync(twin);
-        for (auto& kv : hists) pool.give(kv.second);
-        hists.clear();
-        for (void* p : bin_stale) pool.give(p);
-        bin_stale.clear();
+        class_buffers_to_call_blocks();
         if (shear.d_rot) pool.give(shear.d_rot), shear.d_rot = nullptr;
-        for (void* p : call_blocks) pool.give(p);
-        call_blocks.clear();
+        for (void* p : conv.call_blocks) pool.give(p);
+        conv.call_blocks.clear();
         return rc;
     }
 #undef GDB_DEV
@@ -1982,3 +2047,4 @@ struct Call {
 };
 
 }  // namespace gdb
+

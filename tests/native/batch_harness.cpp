@@ -74,6 +74,31 @@ int gdt_grid_sizes(const gd_batch2d_settings* settings, int32_t n, const double*
     return 0;
 }
 
+// The optimiser's launches of a call whose pair k has grid size F[k] and bandwidth branch branch[k] (classes as the call forms
+// them: grid sizes in order of first appearance, members ascending).  Returns the number of launches; launch q is
+// head[4 q ..] = {F, leading sheared rows, whole, rows}, its plan indices follow one another in ks, the class positions of
+// its non-sheared rows in pos.  -1: more than max_launches.
+int gdt_plan_launches(const int8_t* branch, const int32_t* F, int32_t P, int32_t base_F, int32_t staged, int32_t shear_deferred,
+                      int32_t split_min, int32_t max_launches, int32_t* head, int32_t* ks, int32_t* pos) {
+    std::vector<int> F_list;
+    std::map<int, std::vector<int>> classes;
+    for (int k = 0; k < P; ++k) {
+        if (!classes.count(F[k])) F_list.push_back(F[k]);
+        classes[F[k]].push_back(k);
+    }
+    const std::vector<gdb::Launch> launches = gdb::plan_launches(std::vector<int8_t>(branch, branch + P), F_list, classes, base_F,
+                                                                 staged != 0, shear_deferred != 0, split_min);
+    if ((int)launches.size() > max_launches) return -1;
+    for (size_t q = 0; q < launches.size(); ++q) {
+        const gdb::Launch& L = launches[q];
+        head[4 * q] = L.F, head[4 * q + 1] = L.na, head[4 * q + 2] = L.whole, head[4 * q + 3] = (int32_t)L.ks.size();
+        for (int k : L.ks) *ks++ = k;
+        for (int p : L.pos) *pos++ = p;
+        if (L.d_hist) return -2;  // (the buffers are the caller's to fill)
+    }
+    return (int)launches.size();
+}
+
 int gdt_chol_shear(double c00, double c10, double c11, double* S4, double* r2) { return gdb::chol_shear(c00, c10, c11, S4, r2) ? 0 : 1; }
 
 int gdt_frame_size(int n) { return gdb::frame_size(n); }
