@@ -11,11 +11,10 @@
 // range are served by that XCD's L2.  Unit-weight sample sets use u32 LDS counters (twice the rows per
 // stripe, native ds_add_u32); weighted ones use fp64 LDS atomics (ds_add_f64).
 #include "ctx.hpp"
+#include "binplan.hpp"
 
 #include <array>
 #include <map>
-
-#define LDS_HIST_BYTES (128 * 1024)
 
 // The quotient (x - binmin) / width must be the correctly rounded IEEE quotient (bin indices are bit-exact against
 // numpy), but the divisor is the same for every sample of a column: with y = RN(1 / width) taken once per thread by a
@@ -215,6 +214,17 @@ __device__ __forceinline__ void decode_block_tiles(int B, int nstripes, int nchu
     pair = chunk < nchunks ? unit % B : B;
 }
 
+// rows [lo, hi) of chunk `chunk` when the N rows are cut into nchunks ranges, aligned to 8 samples (empty: a chunk or
+// tile behind the last row)
+__device__ __forceinline__ void chunk_rows(int64_t N, int nchunks, int chunk, int64_t& lo, int64_t& hi) {
+    int64_t per = (N + nchunks - 1) / nchunks;
+    per = (per + 7) & ~(int64_t)7;
+    lo = (int64_t)chunk * per;
+    hi = lo + per;
+    if (hi > N) hi = N;
+    if (hi < lo) hi = lo;
+}
+
 template <typename BinT>
 __device__ __forceinline__ void flush_stripe(const BinT* sh, int row0, int R, int F, double* __restrict__ hist,
                                              bool exclusive) {
@@ -246,12 +256,8 @@ __global__ void __launch_bounds__(1024) k_hist2d(const Hist2DPair* __restrict__ 
     const int row0 = stripe * R;
     for (int i = threadIdx.x; i < R * F; i += blockDim.x) sh[i] = 0;
     __syncthreads();
-    // rows of this chunk, aligned to 8 samples
-    int64_t per = (N + nchunks - 1) / nchunks;
-    per = (per + 7) & ~(int64_t)7;
-    const int64_t lo = (int64_t)chunk * per;
-    int64_t hi = lo + per;
-    if (hi > N) hi = N;
+    int64_t lo, hi;
+    chunk_rows(N, nchunks, chunk, lo, hi);
     if (MODE == 2) {
         const int64_t hi8 = lo + ((hi - lo) & ~(int64_t)7);
         for (int64_t i = lo + 8 * (int64_t)threadIdx.x; i < hi8; i += 8 * (int64_t)blockDim.x) {
@@ -513,14 +519,6 @@ __global__ void __launch_bounds__(256) k_p8_reduce(const unsigned int* __restric
     *reinterpret_cast<double2*>(&hist[i + 2]) = make_double2((double)lo[2], (double)lo[3]);
     *reinterpret_cast<double2*>(&hist[i + 32768]) = make_double2((double)hi[0], (double)hi[1]);
     *reinterpret_cast<double2*>(&hist[i + 32768 + 2]) = make_double2((double)hi[2], (double)hi[3]);
-}
-
-// chunks per pair of the byte-index launch: none for a whole triangle (the partial tables would cost more than the round
-// quantisation), else what fills the rounds (pick_chunks)
-static int pick_chunks(const gd_ctx* ctx, int64_t units, int64_t rows);
-static int u8_chunks(const gd_ctx* ctx, int B, int64_t N) {
-    if (B >= 2 * ctx->cu_count) return 1;
-    return pick_chunks(ctx, B, N);
 }
 
 struct PrebinCol8 {
@@ -833,6 +831,19 @@ static int bucket_route_launch(gd_ctx* ctx, const BucketRoute& R, const BucketRo
 #ifndef P16_UNROLL
 #define P16_UNROLL 4
 #endif
+// A block's packed counters go to its partial table as they are.  A counter that wrapped lowered the sum of all counters, so
+// comparing that sum with the samples the block accepted (nacc, per thread) detects a wrap exactly: the pair is flagged.
+__device__ __forceinline__ void store_packed_partial(const unsigned int* sh, int nwords, unsigned int* __restrict__ dst,
+                                                     unsigned int nacc, double* red, int* flag) {
+    unsigned int total = 0;
+    for (int i = threadIdx.x; i < nwords; i += 1024) {
+        const unsigned int v = sh[i];
+        total += (v & 0xffffu) + (v >> 16);
+        dst[i] = v;
+    }
+    const double t = block_sum((double)total, red), a = block_sum((double)nacc, red);
+    if (threadIdx.x == 0 && t != a) atomicOr(flag, 1);
+}
 template <int MODE>
 __global__ void __launch_bounds__(1024) k_hist2d_f64_p16(const Hist2DPair* __restrict__ pairs, int B, int64_t N, int F, int R,
                                                          int nstripes, int nchunks, int tile_major,
@@ -852,12 +863,8 @@ __global__ void __launch_bounds__(1024) k_hist2d_f64_p16(const Hist2DPair* __res
     const int nwords = (R * F + 1) / 2;
     for (int i = threadIdx.x; i < nwords; i += 1024) sh[i] = 0;
     __syncthreads();
-    int64_t per = (N + nchunks - 1) / nchunks;
-    per = (per + 7) & ~(int64_t)7;
-    const int64_t lo = (int64_t)chunk * per;
-    int64_t hi = lo + per;
-    if (hi > N) hi = N;
-    if (hi < lo) hi = lo;  // (a tile behind the last row)
+    int64_t lo, hi;
+    chunk_rows(N, nchunks, chunk, lo, hi);
     unsigned int nacc = 0;
     auto visit = [&](double xv, double yv) {
         int cx, cy;
@@ -899,15 +906,8 @@ __global__ void __launch_bounds__(1024) k_hist2d_f64_p16(const Hist2DPair* __res
     }
     if (threadIdx.x == 0 && hi2 < hi) visit(P.x[hi2], P.y[hi2]);
     __syncthreads();
-    unsigned int* dst = part + (((int64_t)pair * nchunks + chunk) * nstripes + stripe) * (int64_t)nwords;
-    unsigned int total = 0;
-    for (int i = threadIdx.x; i < nwords; i += 1024) {
-        const unsigned int v = sh[i];
-        total += (v & 0xffffu) + (v >> 16);
-        dst[i] = v;
-    }
-    const double t = block_sum((double)total, red), a = block_sum((double)nacc, red);
-    if (threadIdx.x == 0 && t != a) atomicOr(&overflow[pair], 1);
+    store_packed_partial(sh, nwords, part + (((int64_t)pair * nchunks + chunk) * nstripes + stripe) * (int64_t)nwords, nacc, red,
+                         &overflow[pair]);
 }
 
 // The same packed-counter partials from pre-binned u16 index columns: the few pairs of an up-scaled grid class (F = 384,
@@ -928,11 +928,8 @@ __global__ void __launch_bounds__(1024) k_hist2d_u16_chunks(const Hist2DPair* __
     const int nwords = (R * F + 1) / 2;
     for (int i = threadIdx.x; i < nwords; i += 1024) sh[i] = 0;
     __syncthreads();
-    int64_t per = (N + nchunks - 1) / nchunks;
-    per = (per + 7) & ~(int64_t)7;
-    const int64_t lo = (int64_t)chunk * per;
-    int64_t hi = lo + per;
-    if (hi > N) hi = N;
+    int64_t lo, hi;
+    chunk_rows(N, nchunks, chunk, lo, hi);
     unsigned int nacc = 0;
     auto visit = [&](unsigned cx, unsigned cy) {
         const unsigned r = cy - (unsigned)row0;
@@ -942,7 +939,7 @@ __global__ void __launch_bounds__(1024) k_hist2d_u16_chunks(const Hist2DPair* __
             nacc += 1;
         }
     };
-    const int64_t hi8 = lo < hi ? lo + ((hi - lo) & ~(int64_t)7) : lo;
+    const int64_t hi8 = lo + ((hi - lo) & ~(int64_t)7);
     auto visit8 = [&](const uint4& ax, const uint4& ay) {
         const unsigned xs[4] = {ax.x, ax.y, ax.z, ax.w}, ys[4] = {ay.x, ay.y, ay.z, ay.w};
 #pragma unroll
@@ -979,15 +976,8 @@ __global__ void __launch_bounds__(1024) k_hist2d_u16_chunks(const Hist2DPair* __
     if (threadIdx.x == 0)
         for (int64_t i = hi8; i < hi; ++i) visit(P.ix[i], P.iy[i]);
     __syncthreads();
-    unsigned int* dst = part + (((int64_t)pair * nchunks + chunk) * nstripes + stripe) * (int64_t)nwords;
-    unsigned int total = 0;
-    for (int i = threadIdx.x; i < nwords; i += 1024) {
-        const unsigned int v = sh[i];
-        total += (v & 0xffffu) + (v >> 16);
-        dst[i] = v;
-    }
-    const double t = block_sum((double)total, red), a = block_sum((double)nacc, red);
-    if (threadIdx.x == 0 && t != a) atomicOr(&overflow[pair], 1);
+    store_packed_partial(sh, nwords, part + (((int64_t)pair * nchunks + chunk) * nstripes + stripe) * (int64_t)nwords, nacc, red,
+                         &overflow[pair]);
 }
 
 // hist[pair][row][col] = sum over chunks of the packed partial counters; grid (word blocks, stripes, B).  A thread owns
@@ -1046,17 +1036,8 @@ __global__ void k_minmax_affine(const Hist2DPair* __restrict__ pairs, int64_t N,
     }
 }
 
-// Several sheared pairs share their columns (a correlated block of 5 parameters gives 10 pairs over 5 columns): a group
-// of <= 16 pairs over <= 8 distinct columns reads each column ONCE.  Every thread parks its 16-B loads in its own LDS
-// slots (LDS as indexable per-thread storage: no barrier) and evaluates the pairs from there.
-#define MMG_COLS 8
-#define MMG_PAIRS 16
-struct MinmaxGroup {
-    const double* col[MMG_COLS];
-    double r0[MMG_PAIRS], r1[MMG_PAIRS];
-    int a[MMG_PAIRS], b[MMG_PAIRS];
-    int ncols, npairs;
-};
+// A MinmaxGroup (binplan.hpp) of <= 16 pairs over <= 8 distinct columns reads each column ONCE.  Every thread parks its
+// 16-B loads in its own LDS slots (LDS as indexable per-thread storage: no barrier) and evaluates the pairs from there.
 
 __global__ void __launch_bounds__(256) k_minmax_affine_grouped(const MinmaxGroup* __restrict__ groups, int64_t N,
                                                                double* __restrict__ part) {
@@ -1107,122 +1088,163 @@ __global__ void __launch_bounds__(256) k_minmax_affine_grouped(const MinmaxGroup
 }
 
 // =============================================================================================================
-// How many row chunks to cut every (pair, stripe) unit into.  The 128-KB counter table leaves one block per CU, so a
-// launch runs in ceil(blocks / CUs) rounds of one block time each, and a block's time is proportional to its rows:
-// the cost of c chunks is rounds(c) / c.  (The old rule, "at least two blocks per CU", gave 79 sheared pairs 553
-// blocks = 2.16 -> three rounds of N/7 rows; three chunks give one round of N/3.)  A small penalty per chunk accounts
-// for the zero-fill, flush and reduction of its partial table; at most 16 chunks.
-static int pick_chunks(const gd_ctx* ctx, int64_t units, int64_t rows) {
-    int best = 1;
-    double best_cost = 1e30;
-    for (int c = 1; c <= 16; ++c) {
-        if ((int64_t)c * 65536 > rows && c > 1) break;
-        const int64_t blocks = units * c;
-        const double rounds = (double)((blocks + ctx->cu_count - 1) / ctx->cu_count);
-        const double cost = rounds / c + 0.004 * c;
-        if (cost < best_cost - 1e-12) best_cost = cost, best = c;
+// Host side.  Stripe geometry, chunk counts, block counts and grid sizes come from binplan.hpp.
+
+// Pair tables: from column numbers (the caller has checked them and fills in origins, widths and shear) and from pre-binned
+// index columns.
+static std::vector<Hist2DPair> pairs_of_columns(const gd_ctx* ctx, int B, const int32_t* colx, const int32_t* coly) {
+    std::vector<Hist2DPair> hp((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        memset(&hp[b], 0, sizeof hp[b]);
+        hp[b].x = ctx->cols + (int64_t)colx[b] * ctx->ld;
+        hp[b].y = ctx->cols + (int64_t)coly[b] * ctx->ld;
     }
-    return best;
+    return hp;
+}
+template <class Pair>
+static int pairs_of_indices(gd_ctx* ctx, int B, const void* const* d_idx_x, const void* const* d_idx_y, std::vector<Pair>& hp) {
+    hp.assign((size_t)B, Pair{});
+    for (int b = 0; b < B; ++b) {
+        GD_REQUIRE(d_idx_x[b] && d_idx_y[b], "null index column");
+        hp[b].ix = (decltype(hp[b].ix))d_idx_x[b];
+        hp[b].iy = (decltype(hp[b].iy))d_idx_y[b];
+    }
+    return GD_OK;
+}
+
+static int fetch_flags(gd_ctx* ctx, const int* d_flags, int B, std::vector<int>& hf) {
+    hf.resize((size_t)B);
+    GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
+    return gd_stream_sync(ctx);
 }
 
 template <int MODE>
 static int launch_hist2d(gd_ctx* ctx, int B, const std::vector<Hist2DPair>& hp, int F, double* d_hist, bool allow_p16 = true);
 
-// unit weights, fp64 columns: packed 16-bit counters, partial grids per chunk reduced without atomics; pairs whose
-// counters wrapped are redone with the 32-bit kernel
+// The pairs whose packed counters wrapped (hf[b] != 0) are binned again by the 32-bit kernel into a temporary and copied
+// over their grids in d_hist.
+template <int MODE>
+static int redo_wrapped(gd_ctx* ctx, const std::vector<int>& hf, const std::vector<Hist2DPair>& hp, int F, double* d_hist) {
+    std::vector<int> flagged;
+    std::vector<Hist2DPair> sub;
+    for (size_t b = 0; b < hf.size(); ++b)
+        if (hf[b]) flagged.push_back((int)b), sub.push_back(hp[b]);
+    if (flagged.empty()) return GD_OK;
+    const int nf = (int)flagged.size();
+    const size_t grid = (size_t)F * F;
+    double* tmp = nullptr;
+    GD_HIP(hipMalloc((void**)&tmp, nf * grid * 8));
+    int rc = launch_hist2d<MODE>(ctx, nf, sub, F, tmp, false);
+    for (int q = 0; q < nf && rc == GD_OK; ++q)
+        if (hipMemcpyAsync(d_hist + flagged[q] * grid, tmp + q * grid, grid * 8, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+            rc = gd_fail(ctx, GD_ERR_HIP, "copy of redone histogram failed");
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(tmp);
+    return rc;
+}
+
+// Unit weights, packed 16-bit counters over (pair, chunk of rows, stripe) blocks, the partial grids of the chunks reduced
+// without atomics; pairs whose counters wrapped are redone with the 32-bit kernel.  MODE 0 / 1 bin fp64 columns
+// (k_hist2d_f64_p16), MODE 2 pre-binned u16 index columns (k_hist2d_u16_chunks: the few pairs of an up-scaled grid class).
 template <int MODE>
 static int launch_hist2d_p16(gd_ctx* ctx, int B, const std::vector<Hist2DPair>& hp, int F, double* d_hist) {
-    int R = LDS_HIST_BYTES / (F * 2);
-    if (R > F) R = F;
-    const int nstripes = (F + R - 1) / R;
-    int nchunks = pick_chunks(ctx, (int64_t)B * nstripes, ctx->N);
-    const int nwords = (R * F + 1) / 2;
+    const StripeGeom g = stripe_geom(F, 2);
+    int nchunks = pick_chunks(ctx->cu_count, (int64_t)B * g.nstripes, ctx->N);
     // Many pairs over few columns (the sheared pairs of a triangle: ten pairs per correlated block of five columns): row
     // TILES of 128 K samples, tile-major, so that a column's megabyte is fetched from HBM once for all the pairs that read
     // it; the price is one 128-KB partial table per (pair, tile) through scratch (6 % of the tile's 2 MB of samples).
     int tile_major = 0;
     // Measured (scripts/r04_shear_order.py, 79 pairs, N = 1e7): 2.60 ms against 2.43 ms pair-major -- the kernel is bound by
     // the loads a lane keeps in flight, not by HBM; kept as an experiment switch.
-    if (B >= 16 && nstripes == 1 && ctx->N >= (1 << 20) && getenv("GDHIP_P16_TILE_MAJOR") != nullptr) {
+    if (MODE != 2 && B >= 16 && g.nstripes == 1 && ctx->N >= (1 << 20) && getenv("GDHIP_P16_TILE_MAJOR") != nullptr) {
         int64_t tiles = (ctx->N + 131071) / 131072;
-        const int64_t cap = ((int64_t)3 << 30) / ((int64_t)B * nwords * 4);  // at most 3 GB of partial tables
+        const int64_t cap = ((int64_t)3 << 30) / ((int64_t)B * g.nwords * 4);  // at most 3 GB of partial tables
         if (tiles > cap) tiles = cap;
         if (tiles > nchunks) nchunks = (int)tiles, tile_major = 1;
     }
-    const int units = (B * nchunks + 7) / 8 * 8;
-    const int64_t nblocks = (int64_t)units * nstripes;
+    const unsigned nblocks = (unsigned)unit_blocks(B, nchunks, g.nstripes);
     ScratchPlan sp;
     auto d_pairs = sp.take<Hist2DPair>(B);
     auto d_flags = sp.take<int>(B);
-    auto d_part = sp.take<unsigned int>((int64_t)B * nchunks * nstripes * nwords);
+    auto d_part = sp.take<unsigned int>((int64_t)B * nchunks * g.nstripes * g.nwords);
     GD_TRY(sp.get2(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
     GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
-    GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_f64_p16<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-    k_hist2d_f64_p16<MODE><<<(unsigned)nblocks, 1024, (size_t)nwords * 4, ctx->stream>>>(d_pairs, B, ctx->N, F, R, nstripes,
-                                                                                      nchunks, tile_major, d_part, d_flags);
-    GD_KERNEL_CHECK();
-    k_p16_reduce<<<dim3((unsigned)((nwords + 255) / 256), nstripes, B), 256, 0, ctx->stream>>>(d_part, F, R, nstripes, nchunks, d_hist);
-    GD_KERNEL_CHECK();
-    std::vector<int> hf((size_t)B);
-    GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
-    GD_TRY(gd_stream_sync(ctx));
-    std::vector<int> flagged;
-    for (int b = 0; b < B; ++b)
-        if (hf[b]) flagged.push_back(b);
-    int rc = GD_OK;
-    if (!flagged.empty()) {
-        const int nf = (int)flagged.size();
-        std::vector<Hist2DPair> sub((size_t)nf);
-        for (int q = 0; q < nf; ++q) sub[q] = hp[flagged[q]];
-        double* tmp = nullptr;
-        GD_HIP(hipMalloc((void**)&tmp, (size_t)nf * F * F * 8));
-        rc = launch_hist2d<MODE>(ctx, nf, sub, F, tmp, false);
-        for (int q = 0; q < nf && rc == GD_OK; ++q)
-            if (hipMemcpyAsync(d_hist + (int64_t)flagged[q] * F * F, tmp + (int64_t)q * F * F, (size_t)F * F * 8,
-                               hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-                rc = gd_fail(ctx, GD_ERR_HIP, "copy of redone histogram failed");
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
+    const size_t lds = (size_t)g.nwords * 4;
+    if constexpr (MODE == 2) {
+        GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u16_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
+        k_hist2d_u16_chunks<<<nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->N, F, g.R, g.nstripes, nchunks, d_part, d_flags);
+    } else {
+        GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_f64_p16<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
+        k_hist2d_f64_p16<MODE><<<nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->N, F, g.R, g.nstripes, nchunks, tile_major, d_part,
+                                                                    d_flags);
     }
-    return rc;
+    GD_KERNEL_CHECK();
+    k_p16_reduce<<<dim3((unsigned)((g.nwords + 255) / 256), g.nstripes, B), 256, 0, ctx->stream>>>(d_part, F, g.R, g.nstripes, nchunks, d_hist);
+    GD_KERNEL_CHECK();
+    std::vector<int> hf;
+    GD_TRY(fetch_flags(ctx, d_flags, B, hf));
+    return redo_wrapped<MODE>(ctx, hf, hp, F, d_hist);
 }
 
+// The 32-bit (unit or integral weights: exact u32 counters, twice the rows per stripe) or fp64 stripe kernel; unit-weight
+// fp64 columns go to the packed counters above unless this IS their redo (allow_p16 = false).
 template <int MODE>
 static int launch_hist2d(gd_ctx* ctx, int B, const std::vector<Hist2DPair>& hp, int F, double* d_hist, bool allow_p16) {
     GD_REQUIRE(F >= 2 && F <= 4096, "fine_bins_2D out of range");
     const bool has_w = ctx->w != nullptr;
-    if (MODE != 2 && !has_w && allow_p16 && !getenv("GDHIP_NO_P16")) return launch_hist2d_p16<(MODE == 2 ? 0 : MODE)>(ctx, B, hp, F, d_hist);
-    const bool u32bins = !has_w || ctx->w_integral;  // integral weights: exact u32 counters, twice the rows per stripe
+    if (MODE != 2 && !has_w && allow_p16 && !getenv("GDHIP_NO_P16")) return launch_hist2d_p16<MODE>(ctx, B, hp, F, d_hist);
+    const bool u32bins = !has_w || ctx->w_integral;
     const int binbytes = u32bins ? 4 : 8;
-    int R = LDS_HIST_BYTES / (F * binbytes);
-    GD_REQUIRE(R >= 1, "fine_bins_2D too large for the LDS stripe");
-    if (R > F) R = F;
-    const int nstripes = (F + R - 1) / R;
-    const int nchunks = pick_chunks(ctx, (int64_t)B * nstripes, ctx->N);
-    const int units = (B * nchunks + 7) / 8 * 8;
-    const int64_t nblocks = (int64_t)units * nstripes;
-    Hist2DPair* d_pairs = (Hist2DPair*)gd_scratch2(ctx, (int64_t)B * sizeof(Hist2DPair));
-    if (!d_pairs) return GD_ERR_NOMEM;
+    const StripeGeom g = stripe_geom(F, binbytes);
+    GD_REQUIRE(g.R >= 1, "fine_bins_2D too large for the LDS stripe");
+    const int nchunks = pick_chunks(ctx->cu_count, (int64_t)B * g.nstripes, ctx->N);
+    ScratchPlan sp;
+    auto d_pairs = sp.tail<Hist2DPair>(B);
+    GD_TRY(sp.get2(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
     if (nchunks > 1) GD_HIP(hipMemsetAsync(d_hist, 0, (size_t)B * F * F * 8, ctx->stream));
-    const size_t lds = (size_t)R * F * binbytes;
-    if (has_w && !u32bins) {
-        auto kern = k_hist2d<MODE, true, double>;
+    auto run = [&](auto kern) -> int {
         GD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-        kern<<<(unsigned)nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->w, ctx->N, F, R, nstripes, nchunks, d_hist);
-    } else if (has_w) {
-        auto kern = k_hist2d<MODE, true, unsigned int>;
-        GD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-        kern<<<(unsigned)nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->w, ctx->N, F, R, nstripes, nchunks, d_hist);
-    } else {
-        auto kern = k_hist2d<MODE, false, unsigned int>;
-        GD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-        kern<<<(unsigned)nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, nullptr, ctx->N, F, R, nstripes, nchunks,
-                                                            d_hist);
-    }
+        kern<<<(unsigned)unit_blocks(B, nchunks, g.nstripes), 1024, (size_t)g.R * F * binbytes, ctx->stream>>>(
+            d_pairs, B, ctx->w, ctx->N, F, g.R, g.nstripes, nchunks, d_hist);
+        return GD_OK;
+    };
+    if (has_w && !u32bins)
+        GD_TRY(run(k_hist2d<MODE, true, double>));
+    else if (has_w)
+        GD_TRY(run(k_hist2d<MODE, true, unsigned int>));
+    else
+        GD_TRY(run(k_hist2d<MODE, false, unsigned int>));
     GD_KERNEL_CHECK();
     GD_TRY(gd_stream_sync(ctx));  // hp / d_pairs lifetime
+    return GD_OK;
+}
+
+// The requested index columns split in two: those served from their bucket columns (R) and those the fp64 kernel bins
+// (hc; fp_of[c] = column c's slot there or -1).  The caller has checked the column numbers.
+template <class Col>
+struct PrebinSplit {
+    BucketRoute R;
+    std::vector<Col> hc;
+    std::vector<int> fp_of;
+};
+template <class Col>
+static int prebin_split(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width,
+                        void* const* d_idx, PrebinSplit<Col>& S) {
+    for (int c = 0; c < ncols; ++c) GD_REQUIRE(d_idx[c], "null index buffer");
+    S.R = bucket_route(ctx, cols, ncols, binmin, width, d_idx);
+    S.fp_of.assign((size_t)ncols, -1);
+    for (int c = 0; c < ncols; ++c) {
+        if (S.R.slot_of[c] >= 0) continue;
+        Col r;
+        r.x = ctx->cols + (int64_t)cols[c] * ctx->ld;
+        r.idx = (decltype(r.idx))d_idx[c];
+        r.binmin = binmin[c];
+        r.width = width[c];
+        S.fp_of[c] = (int)S.hc.size();
+        S.hc.push_back(r);
+    }
     return GD_OK;
 }
 
@@ -1275,7 +1297,8 @@ int gd_hist1d_dev(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double*
 int gd_bin_indices(gd_ctx* ctx, int32_t col, double binmin, double width, int32_t round_half, int32_t F,
                    int32_t* idx_out, int64_t* n_out_of_range) {
     GD_REQUIRE(ctx && idx_out, "bad argument");
-    GD_REQUIRE(ctx->cols && col >= 0 && col < ctx->n + GD_EXTRA_COLS, "bad column");
+    GD_REQUIRE(ctx->cols, "no samples uploaded");
+    GD_REQUIRE_COLUMNS(&col, 1);
     ScratchPlan sp;
     auto d_bad = sp.take<unsigned long long>(1);
     auto d_idx = sp.tail<int32_t>(ctx->N);
@@ -1296,7 +1319,8 @@ int gd_bin_indices(gd_ctx* ctx, int32_t col, double binmin, double width, int32_
 
 int gd_prebin(gd_ctx* ctx, int32_t col, double binmin, double width, int32_t F, void* d_idx_u16) {
     GD_REQUIRE(ctx && d_idx_u16, "bad argument");
-    GD_REQUIRE(ctx->cols && col >= 0 && col < ctx->n + GD_EXTRA_COLS, "bad column");
+    GD_REQUIRE(ctx->cols, "no samples uploaded");
+    GD_REQUIRE_COLUMNS(&col, 1);
     GD_REQUIRE(F >= 2 && F < 65535, "F out of range for u16 indices");
     {
         void* const idx1[1] = {d_idx_u16};
@@ -1319,20 +1343,11 @@ int gd_prebin_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doubl
     GD_REQUIRE(ctx && cols && binmin && width && d_idx_u16 && ncols > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
     GD_REQUIRE(F >= 2 && F < 65535, "F out of range for u16 indices");
-    for (int c = 0; c < ncols; ++c)
-        GD_REQUIRE(cols[c] >= 0 && cols[c] < ctx->n + GD_EXTRA_COLS && d_idx_u16[c], "bad column / null index buffer");
-    const BucketRoute R = bucket_route(ctx, cols, ncols, binmin, width, d_idx_u16);
-    std::vector<PrebinCol> hc;
-    for (int c = 0; c < ncols; ++c) {
-        if (R.slot_of[c] >= 0) continue;
-        PrebinCol r;
-        r.x = ctx->cols + (int64_t)cols[c] * ctx->ld;
-        r.idx = (unsigned short*)d_idx_u16[c];
-        r.binmin = binmin[c];
-        r.width = width[c];
-        hc.push_back(r);
-    }
-    const int nfp = (int)hc.size();
+    GD_REQUIRE_COLUMNS(cols, ncols);
+    PrebinSplit<PrebinCol> S;
+    GD_TRY(prebin_split(ctx, cols, ncols, binmin, width, d_idx_u16, S));
+    const BucketRoute& R = S.R;
+    const int nfp = (int)S.hc.size();
     BucketRouteLayout L(ctx, R);
     ScratchPlan sp;
     auto d_c = sp.take<PrebinCol>(nfp);
@@ -1340,11 +1355,8 @@ int gd_prebin_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doubl
     GD_TRY(sp.get2(ctx));
     L.sp.place(d_route);
     if (nfp) {
-        GD_TRY(gd_h2d(ctx, d_c, hc.data(), (size_t)nfp * sizeof(PrebinCol)));
-        int nblk = (int)((ctx->N / 8 + 255) / 256);  // one 8-sample iteration per thread at most, like the single-column kernel
-        if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-        if (nblk < 1) nblk = 1;
-        k_prebin_batch<<<dim3(nblk, nfp), 256, 0, ctx->stream>>>(d_c, ctx->N, F);
+        GD_TRY(gd_h2d(ctx, d_c, S.hc.data(), (size_t)nfp * sizeof(PrebinCol)));
+        k_prebin_batch<<<dim3(prebin_blocks(ctx->cu_count, ctx->N), nfp), 256, 0, ctx->stream>>>(d_c, ctx->N, F);
         GD_KERNEL_CHECK();
     }
     if (!R.recs.empty()) {
@@ -1359,45 +1371,33 @@ int gd_hist2d(gd_ctx* ctx, int32_t B, const int32_t* colx, const int32_t* coly, 
               const double* widthx, const double* binminy, const double* widthy, int32_t F, void* d_hist) {
     GD_REQUIRE(ctx && colx && coly && binminx && widthx && binminy && widthy && d_hist && B > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
-    std::vector<Hist2DPair> hp((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        GD_REQUIRE(colx[b] >= 0 && colx[b] < ctx->n + GD_EXTRA_COLS && coly[b] >= 0 && coly[b] < ctx->n + GD_EXTRA_COLS, "column out of range");
-        Hist2DPair& p = hp[b];
-        memset(&p, 0, sizeof p);
-        p.x = ctx->cols + (int64_t)colx[b] * ctx->ld;
-        p.y = ctx->cols + (int64_t)coly[b] * ctx->ld;
-        p.bx = binminx[b], p.wx = widthx[b], p.by = binminy[b], p.wy = widthy[b];
-    }
+    GD_REQUIRE_COLUMNS(colx, B);
+    GD_REQUIRE_COLUMNS(coly, B);
+    std::vector<Hist2DPair> hp = pairs_of_columns(ctx, B, colx, coly);
+    for (int b = 0; b < B; ++b) hp[b].bx = binminx[b], hp[b].wx = widthx[b], hp[b].by = binminy[b], hp[b].wy = widthy[b];
     return launch_hist2d<0>(ctx, B, hp, F, (double*)d_hist);
 }
 
-static int launch_hist2d_u16(gd_ctx* ctx, int B, const std::vector<Hist2DPair>& hp, int F, double* d_hist,
-                             std::vector<int>& flagged) {
-    int R = LDS_HIST_BYTES / (F * 2);
-    if (R > F) R = F;
-    const int nstripes = (F + R - 1) / R;
-    const int units = (B + 7) / 8 * 8;
-    const int64_t nblocks = (int64_t)units * nstripes;
+// unit weights or byte multiplicities, batched: one block per (pair, stripe), 16-bit packed LDS counters, exact overflow
+// detection, 32-bit redo for flagged pairs
+static int launch_hist2d_u16(gd_ctx* ctx, int B, const std::vector<Hist2DPair>& hp, int F, double* d_hist) {
+    const StripeGeom g = stripe_geom(F, 2);
     ScratchPlan sp;
     auto d_pairs = sp.take<Hist2DPair>(B);
     auto d_flags = sp.tail<int>(B);
     GD_TRY(sp.get2(ctx));
     GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
     GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
-    const size_t lds = ((size_t)R * F + 1) / 2 * 4;
     GD_TRY(gd_by_flag(ctx->w8 != nullptr, [&](auto HW8) -> int {
         GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u16<HW8.value>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-        k_hist2d_u16<HW8.value><<<(unsigned)nblocks, 1024, lds, ctx->stream>>>(d_pairs, B, ctx->N, F, R, nstripes, ctx->w8, d_hist, d_flags);
+        k_hist2d_u16<HW8.value><<<(unsigned)unit_blocks(B, 1, g.nstripes), 1024, (size_t)g.nwords * 4, ctx->stream>>>(
+            d_pairs, B, ctx->N, F, g.R, g.nstripes, ctx->w8, d_hist, d_flags);
         return GD_OK;
     }));
     GD_KERNEL_CHECK();
-    std::vector<int> hf((size_t)B);
-    GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
-    GD_TRY(gd_stream_sync(ctx));
-    flagged.clear();
-    for (int b = 0; b < B; ++b)
-        if (hf[b]) flagged.push_back(b);
-    return GD_OK;
+    std::vector<int> hf;
+    GD_TRY(fetch_flags(ctx, d_flags, B, hf));
+    return redo_wrapped<2>(ctx, hf, hp, F, d_hist);
 }
 
 int gd_hist2d_prebinned(gd_ctx* ctx, int32_t B, const void* const* d_idx_x, const void* const* d_idx_y, int32_t F,
@@ -1405,139 +1405,102 @@ int gd_hist2d_prebinned(gd_ctx* ctx, int32_t B, const void* const* d_idx_x, cons
     GD_REQUIRE(ctx && d_idx_x && d_idx_y && d_hist && B > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
     GD_REQUIRE(F >= 2 && F <= 4096, "fine_bins_2D out of range");
-    std::vector<Hist2DPair> hp((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        Hist2DPair& p = hp[b];
-        memset(&p, 0, sizeof p);
-        p.ix = (const unsigned short*)d_idx_x[b];
-        p.iy = (const unsigned short*)d_idx_y[b];
-        GD_REQUIRE(p.ix && p.iy, "null index column");
-    }
-    {
-        int R16 = LDS_HIST_BYTES / (F * 2);
-        if (R16 > F) R16 = F;
-        const int nstripes16 = (F + R16 - 1) / R16;
-        if (!ctx->w && (int64_t)B * nstripes16 < ctx->cu_count && !getenv("GDHIP_NO_U16_CHUNKS")) {
-            // few pairs (the up-scaled grid classes): packed counters over (pair, chunk of rows, stripe) blocks, partials
-            // reduced without atomics; pairs whose counters wrapped are redone with the 32-bit kernel
-            const int R = R16, nstripes = nstripes16;
-            const int nchunks = pick_chunks(ctx, (int64_t)B * nstripes, ctx->N);
-            const int units = (B * nchunks + 7) / 8 * 8;
-            const int64_t nblocks = (int64_t)units * nstripes;
-            const int nwords = (R * F + 1) / 2;
-            ScratchPlan sp;
-            auto d_pairs = sp.take<Hist2DPair>(B);
-            auto d_flags = sp.take<int>(B);
-            auto d_part = sp.tail<unsigned int>((int64_t)B * nchunks * nstripes * nwords);
-            GD_TRY(sp.get2(ctx));
-            GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
-            GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
-            GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u16_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES));
-            k_hist2d_u16_chunks<<<(unsigned)nblocks, 1024, (size_t)nwords * 4, ctx->stream>>>(d_pairs, B, ctx->N, F, R, nstripes, nchunks,
-                                                                                              d_part, d_flags);
-            GD_KERNEL_CHECK();
-            k_p16_reduce<<<dim3((unsigned)((nwords + 255) / 256), nstripes, B), 256, 0, ctx->stream>>>(d_part, F, R, nstripes, nchunks, (double*)d_hist);
-            GD_KERNEL_CHECK();
-            std::vector<int> hf((size_t)B);
-            GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
-            GD_TRY(gd_stream_sync(ctx));
-            std::vector<int> flagged;
-            for (int b = 0; b < B; ++b)
-                if (hf[b]) flagged.push_back(b);
-            int rc = GD_OK;
-            if (!flagged.empty()) {
-                const int nf = (int)flagged.size();
-                std::vector<Hist2DPair> sub((size_t)nf);
-                for (int q = 0; q < nf; ++q) sub[q] = hp[flagged[q]];
-                double* tmp = nullptr;
-                GD_HIP(hipMalloc((void**)&tmp, (size_t)nf * F * F * 8));
-                rc = launch_hist2d<2>(ctx, nf, sub, F, tmp);
-                for (int q = 0; q < nf && rc == GD_OK; ++q)
-                    if (hipMemcpyAsync((double*)d_hist + (int64_t)flagged[q] * F * F, tmp + (int64_t)q * F * F, (size_t)F * F * 8,
-                                       hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-                        rc = gd_fail(ctx, GD_ERR_HIP, "copy of redone histogram failed");
-                (void)hipStreamSynchronize(ctx->stream);
-                (void)hipFree(tmp);
-            }
-            return rc;
-        }
-        // (real weights: four stripe passes with ds_add_f64.  Round 5 measured a one-pass alternative -- samples partitioned by
-        // stripe once per y column into 16-byte records (row, row in stripe, weight), a (pair, stripe) block walking only its
-        // quarter -- at 43.6 ms per 1225 pairs against 41.3 ms here: 16 bytes per (sample, pair) make it bound by the L2-miss
-        // path (80 GB per 400-pair launch at 0.74 of the peak; with the pairs of a y column on one XCD 42 GB, but 19 ms).  The
-        // roof of the adds themselves is 7.8 ms (2.5 ds_add_f64 lanes per clock and CU, scripts/micro/lds_atomic_f64_roof.hip);
-        // what keeps both forms away from it is the 12-16 bytes every (sample, pair) visit must fetch.  Not kept; DESIGN.md.)
-        // the 16-bit kernel gives each (pair, stripe) to ONE block: only worth it when that fills the chip
-        if ((ctx->w && !ctx->w8) || (int64_t)B * nstripes16 < ctx->cu_count)
-            return launch_hist2d<2>(ctx, B, hp, F, (double*)d_hist);
-    }
-    // unit weights or byte multiplicities, batched: 16-bit packed LDS counters, exact overflow detection, 32-bit redo
-    // for flagged pairs
-    std::vector<int> flagged;
-    int rc = launch_hist2d_u16(ctx, B, hp, F, (double*)d_hist, flagged);
-    if (rc) return rc;
-    if (!flagged.empty()) {
-        const int nf = (int)flagged.size();
-        std::vector<Hist2DPair> sub((size_t)nf);
-        for (int q = 0; q < nf; ++q) sub[q] = hp[flagged[q]];
-        double* tmp = nullptr;
-        GD_HIP(hipMalloc((void**)&tmp, (size_t)nf * F * F * 8));
-        rc = launch_hist2d<2>(ctx, nf, sub, F, tmp);
-        if (rc == GD_OK)
-            for (int q = 0; q < nf && rc == GD_OK; ++q)
-                if (hipMemcpyAsync((double*)d_hist + (int64_t)flagged[q] * F * F, tmp + (int64_t)q * F * F, (size_t)F * F * 8,
-                                   hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-                    rc = gd_fail(ctx, GD_ERR_HIP, "copy of redone histogram failed");
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(tmp);
-    }
-    return rc;
+    std::vector<Hist2DPair> hp;
+    GD_TRY(pairs_of_indices(ctx, B, d_idx_x, d_idx_y, hp));
+    // the 16-bit kernel gives each (pair, stripe) to ONE block: only worth it when that fills the chip
+    const bool fills_chip = (int64_t)B * stripe_geom(F, 2).nstripes >= ctx->cu_count;
+    // few pairs (the up-scaled grid classes): the rows are cut into chunks as well
+    if (!ctx->w && !fills_chip && !getenv("GDHIP_NO_U16_CHUNKS")) return launch_hist2d_p16<2>(ctx, B, hp, F, (double*)d_hist);
+    // (real weights: four stripe passes with ds_add_f64.  Round 5 measured a one-pass alternative -- samples partitioned by
+    // stripe once per y column into 16-byte records (row, row in stripe, weight), a (pair, stripe) block walking only its
+    // quarter -- at 43.6 ms per 1225 pairs against 41.3 ms here: 16 bytes per (sample, pair) make it bound by the L2-miss
+    // path (80 GB per 400-pair launch at 0.74 of the peak; with the pairs of a y column on one XCD 42 GB, but 19 ms).  The
+    // roof of the adds themselves is 7.8 ms (2.5 ds_add_f64 lanes per clock and CU, scripts/micro/lds_atomic_f64_roof.hip);
+    // what keeps both forms away from it is the 12-16 bytes every (sample, pair) visit must fetch.  Not kept; DESIGN.md.)
+    if ((ctx->w && !ctx->w8) || !fills_chip) return launch_hist2d<2>(ctx, B, hp, F, (double*)d_hist);
+    return launch_hist2d_u16(ctx, B, hp, F, (double*)d_hist);
 }
 
-// The launches of gd_prebin8_batch on ctx->stream, nothing waited for: columns whose bucket columns are valid (the quantile
-// select has walked them) are binned from those 2 bytes per sample, the others by the fp64 kernel.  One function for the call
-// that waits (gd_prebin8_batch) and the one that does not (gd_prebin8_enqueue).
-struct Prebin8Launch {
-    BucketRoute R;
-    std::vector<int> fp_of;  // per requested column: its slot among the fp64 kernel's columns or -1
-    int nfp = 0;
-    unsigned long long *d_bad = nullptr, *d_bad_bq = nullptr;  // out-of-range counts of the two routes (device scratch)
+// ONE stream-ordered sequence behind the four byte-index entry points, nothing waited for: the pre-binning of `ncols` columns
+// (from their bucket columns where the quantile select has walked them, else by the fp64 kernel) and the unit-weight binning
+// of B pairs at F = 256.  Both tables go up in ONE staged copy, the out-of-range counters and the wrap flags are zeroed in
+// ONE fill; ncols == 0 and B == 0 are the degenerate cases.  Column c's out-of-range count is word bad_slot(c) of the
+// counters, the fp64 route's (d_bad) in front of the bucket route's (d_bad_bq).
+struct ByteLaunch {
+    PrebinSplit<PrebinCol8> S;
+    int nfp = 0, nbq = 0;  // columns of the fp64 kernel / of the bucket route
+    unsigned long long *d_bad = nullptr, *d_bad_bq = nullptr;
+    int* d_flags = nullptr;
+    int bad_slot(int c) const { return S.R.slot_of[c] >= 0 ? nfp + S.R.slot_of[c] : S.fp_of[c]; }
 };
-static int prebin8_launch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width, int32_t F,
-                          void* const* d_idx_out, Prebin8Launch& PL) {
-    PL.R = bucket_route(ctx, cols, ncols, binmin, width, d_idx_out);
-    const BucketRoute& R = PL.R;
-    std::vector<PrebinCol8> hc;
-    PL.fp_of.assign((size_t)ncols, -1);
-    for (int c = 0; c < ncols; ++c) {
-        if (R.slot_of[c] >= 0) continue;
-        PrebinCol8 r;
-        r.x = ctx->cols + (int64_t)cols[c] * ctx->ld;
-        r.idx = (unsigned char*)d_idx_out[c];
-        r.binmin = binmin[c];
-        r.width = width[c];
-        PL.fp_of[c] = (int)hc.size();
-        hc.push_back(r);
-    }
-    const int nfp = PL.nfp = (int)hc.size();
+static int byte_launch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width, int F,
+                       void* const* d_idx_out, int B, const void* const* d_idx_x, const void* const* d_idx_y, double* d_hist,
+                       ByteLaunch& BL) {
+    std::vector<Hist2DPair8> hp;
+    GD_TRY(pairs_of_indices(ctx, B, d_idx_x, d_idx_y, hp));
+    if (ncols) GD_TRY(prebin_split(ctx, cols, ncols, binmin, width, d_idx_out, BL.S));
+    const BucketRoute& R = BL.S.R;
+    const int nfp = BL.nfp = (int)BL.S.hc.size();
+    BL.nbq = (int)R.recs.size();
+    const int nchunks = B ? u8_chunks(ctx->cu_count, B, ctx->N) : 1;
     BucketRouteLayout L(ctx, R);
     ScratchPlan sp;
     auto d_c = sp.take<PrebinCol8>(nfp);
+    auto d_pairs = sp.take<Hist2DPair8>(B);
+    const int64_t table_bytes = sp.bytes();  // the two tables go up in one copy
     auto d_bad = sp.take<unsigned long long>(nfp);
-    auto d_route = sp.tail<char>(L.sp.bytes());
+    auto d_flags = sp.take<int>(B);
+    const int64_t zero_bytes = sp.bytes() - table_bytes;  // the counters and the flags are zeroed in one fill
+    auto d_part = sp.take<unsigned int>(nchunks > 1 ? (int64_t)B * nchunks * 32768 : 0);
+    auto d_route = sp.take<char>(L.sp.bytes());
     GD_TRY(sp.get2(ctx));
     L.sp.place(d_route);
-    if (nfp) {
-        GD_TRY(gd_h2d(ctx, d_c, hc.data(), (size_t)nfp * sizeof(PrebinCol8)));
-        GD_HIP(hipMemsetAsync(d_bad, 0, (size_t)nfp * 8, ctx->stream));
-        int nblk = (int)((ctx->N / 8 + 255) / 256);
-        if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-        if (nblk < 1) nblk = 1;
-        k_prebin8_batch<<<dim3(nblk, nfp), 256, 0, ctx->stream>>>(d_c, ctx->N, F, d_bad);
-        GD_KERNEL_CHECK();
-        PL.d_bad = d_bad;
+    if (table_bytes) {
+        std::vector<char> tab((size_t)table_bytes, 0);
+        if (nfp) memcpy(tab.data() + d_c.off, BL.S.hc.data(), (size_t)nfp * sizeof(PrebinCol8));
+        if (B) memcpy(tab.data() + d_pairs.off, hp.data(), (size_t)B * sizeof(Hist2DPair8));
+        GD_TRY(gd_stage_h2d(ctx, d_c, tab.data(), (size_t)table_bytes));
     }
-    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, L, F, &PL.d_bad_bq));
+    if (zero_bytes) GD_HIP(hipMemsetAsync(d_bad, 0, (size_t)zero_bytes, ctx->stream));
+    if (nfp) {
+        k_prebin8_batch<<<dim3(prebin_blocks(ctx->cu_count, ctx->N), nfp), 256, 0, ctx->stream>>>(d_c, ctx->N, F, d_bad);
+        GD_KERNEL_CHECK();
+    }
+    if (BL.nbq) GD_TRY(bucket_route_launch<true>(ctx, R, L, F, &BL.d_bad_bq));
+    if (B) {
+        GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u8_pf<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES + 128));
+        k_hist2d_u8_pf<3><<<(unsigned)unit_blocks(B, nchunks), 1024, LDS_HIST_BYTES + 128, ctx->stream>>>(d_pairs, B, ctx->N, d_hist, d_flags,
+                                                                                                         nchunks, d_part);
+        GD_KERNEL_CHECK();
+        if (nchunks > 1) {
+            k_p8_reduce<<<dim3(32, B), 256, 0, ctx->stream>>>(d_part, nchunks, d_hist);
+            GD_KERNEL_CHECK();
+        }
+    }
+    BL.d_bad = d_bad, BL.d_flags = d_flags;
+    return GD_OK;
+}
+
+static int require_inside_grid(gd_ctx* ctx, const int64_t* bad, int ncols) {
+    int64_t nbad = 0;
+    for (int c = 0; c < ncols; ++c) nbad += bad[c];
+    if (nbad) return gd_fail(ctx, GD_ERR_SOLVER, "%lld samples outside the byte-index grid: use the u16 path", (long long)nbad);
+    return GD_OK;
+}
+
+// The ONE wait behind byte_launch: the out-of-range counts go to bad_out; where pairs were binned, samples outside the grid
+// and wrapped counters -- either leaves the histograms wrong -- are errors.
+static int byte_wait(gd_ctx* ctx, const ByteLaunch& BL, int ncols, int64_t* bad_out, int B) {
+    std::vector<unsigned long long> hbad((size_t)(BL.nfp + BL.nbq));
+    std::vector<int> hf((size_t)B);
+    if (BL.nfp) GD_TRY(gd_fetch(ctx, hbad.data(), BL.d_bad, (size_t)BL.nfp * 8));
+    if (BL.nbq) GD_TRY(gd_fetch(ctx, hbad.data() + BL.nfp, BL.d_bad_bq, (size_t)BL.nbq * 8));
+    if (B) GD_TRY(gd_fetch(ctx, hf.data(), BL.d_flags, (size_t)B * 4));
+    GD_TRY(gd_stream_sync(ctx));
+    for (int c = 0; c < ncols; ++c) bad_out[c] = (int64_t)hbad[BL.bad_slot(c)];
+    if (B) GD_TRY(require_inside_grid(ctx, bad_out, ncols));
+    for (int b = 0; b < B; ++b)
+        if (hf[b]) return gd_fail(ctx, GD_ERR_SOLVER, "16-bit bin counter wrapped in pair %d: redo with gd_hist2d_prebinned", b);
     return GD_OK;
 }
 
@@ -1546,31 +1509,24 @@ int gd_prebin8_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const doub
     GD_REQUIRE(ctx && cols && binmin && width && d_idx_out && bad_out && ncols > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
     GD_REQUIRE(F >= 2 && F <= 256, "byte indices need fine_bins_2D <= 256");
-    for (int c = 0; c < ncols; ++c) GD_REQUIRE(cols[c] >= 0 && cols[c] < ctx->n + GD_EXTRA_COLS && d_idx_out[c], "bad column");
-    Prebin8Launch PL;
-    GD_TRY(prebin8_launch(ctx, cols, ncols, binmin, width, F, d_idx_out, PL));
-    const int nfp = PL.nfp;
-    std::vector<unsigned long long> hb((size_t)nfp), hq(PL.R.recs.size());
-    if (nfp) GD_TRY(gd_fetch(ctx, hb.data(), PL.d_bad, (size_t)nfp * 8));
-    if (!PL.R.recs.empty()) GD_TRY(gd_fetch(ctx, hq.data(), PL.d_bad_bq, hq.size() * 8));
-    GD_TRY(gd_stream_sync(ctx));
-    for (int c = 0; c < ncols; ++c) bad_out[c] = (int64_t)(PL.R.slot_of[c] >= 0 ? hq[PL.R.slot_of[c]] : hb[PL.fp_of[c]]);
-    return GD_OK;
+    GD_REQUIRE_COLUMNS(cols, ncols);
+    ByteLaunch BL;
+    GD_TRY(byte_launch(ctx, cols, ncols, binmin, width, F, d_idx_out, 0, nullptr, nullptr, nullptr, BL));
+    return byte_wait(ctx, BL, ncols, bad_out, 0);
 }
 
-// bad_pinned: 2 x ncols words of page-locked memory; column c's count arrives in word PL-slot order, so the caller reads
-// bad_pinned[c] through the map this returns in the second half: bad_pinned[ncols + c] = index of column c's word
+// Enqueued, not waited for.  bad_pinned: 2 x ncols words of page-locked memory; the counts arrive in the launch's slot order,
+// so the caller reads column c's through the map in the second half: bad_pinned[ncols + c] = index of column c's word
 int gd_prebin8_enqueue(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* binmin, const double* width,
                        void* const* d_idx_out, unsigned long long* bad_pinned) {
     GD_REQUIRE(ctx && cols && binmin && width && d_idx_out && bad_pinned && ncols > 0, "bad argument");
     GD_REQUIRE(ctx->cols && !ctx->w, "index columns are enqueued ahead for unit weights only");
-    for (int c = 0; c < ncols; ++c) GD_REQUIRE(cols[c] >= 0 && cols[c] < ctx->n && d_idx_out[c], "bad column");
-    Prebin8Launch PL;
-    GD_TRY(prebin8_launch(ctx, cols, ncols, binmin, width, 256, d_idx_out, PL));
-    const int nfp = PL.nfp;
-    for (int c = 0; c < ncols; ++c) bad_pinned[ncols + c] = (unsigned long long)(PL.R.slot_of[c] >= 0 ? nfp + PL.R.slot_of[c] : PL.fp_of[c]);
-    if (nfp) GD_TRY(gd_fetch_pinned(ctx, bad_pinned, PL.d_bad, (size_t)nfp * 8));
-    if (!PL.R.recs.empty()) GD_TRY(gd_fetch_pinned(ctx, bad_pinned + nfp, PL.d_bad_bq, PL.R.recs.size() * 8));
+    GD_REQUIRE_SAMPLE_COLUMNS(cols, ncols);
+    ByteLaunch BL;
+    GD_TRY(byte_launch(ctx, cols, ncols, binmin, width, 256, d_idx_out, 0, nullptr, nullptr, nullptr, BL));
+    for (int c = 0; c < ncols; ++c) bad_pinned[ncols + c] = (unsigned long long)BL.bad_slot(c);
+    if (BL.nfp) GD_TRY(gd_fetch_pinned(ctx, bad_pinned, BL.d_bad, (size_t)BL.nfp * 8));
+    if (BL.nbq) GD_TRY(gd_fetch_pinned(ctx, bad_pinned + BL.nfp, BL.d_bad_bq, (size_t)BL.nbq * 8));
     return GD_OK;
 }
 
@@ -1945,36 +1901,9 @@ int gd_hist2d_prebinned8(gd_ctx* ctx, int32_t B, const void* const* d_idx_x, con
         for (int b = 0; b < B; ++b) GD_REQUIRE(d_idx_x[b] && d_idx_y[b], "null index column");
         return hist2d_weighted_sorted(ctx, B, d_idx_x, d_idx_y, (double*)d_hist);
     }
-    const int F = 256;
-    std::vector<Hist2DPair8> hp((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        hp[b].ix = (const unsigned char*)d_idx_x[b];
-        hp[b].iy = (const unsigned char*)d_idx_y[b];
-        GD_REQUIRE(hp[b].ix && hp[b].iy, "null index column");
-    }
-    const int nchunks = u8_chunks(ctx, B, ctx->N);
-    ScratchPlan sp;
-    auto d_pairs = sp.take<Hist2DPair8>(B);
-    auto d_flags = sp.take<int>(B);
-    auto d_part = sp.tail<unsigned int>(nchunks > 1 ? (int64_t)B * nchunks * 32768 : 0);
-    GD_TRY(sp.get2(ctx));
-    GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair8)));
-    GD_HIP(hipMemsetAsync(d_flags, 0, (size_t)B * 4, ctx->stream));
-    const int nblocks = (B * nchunks + 7) / 8 * 8;
-    GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u8_pf<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES + 128));
-    k_hist2d_u8_pf<3><<<nblocks, 1024, LDS_HIST_BYTES + 128, ctx->stream>>>(d_pairs, B, ctx->N, (double*)d_hist, d_flags, nchunks, d_part);
-    GD_KERNEL_CHECK();
-    if (nchunks > 1) {
-        k_p8_reduce<<<dim3(32, B), 256, 0, ctx->stream>>>(d_part, nchunks, (double*)d_hist);
-        GD_KERNEL_CHECK();
-    }
-    std::vector<int> hf((size_t)B);
-    GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
-    GD_TRY(gd_stream_sync(ctx));
-    int rc = GD_OK;
-    for (int b = 0; b < B && rc == GD_OK; ++b)
-        if (hf[b]) rc = gd_fail(ctx, GD_ERR_SOLVER, "16-bit bin counter wrapped in pair %d: redo with gd_hist2d_prebinned", b);
-    return rc;
+    ByteLaunch BL;
+    GD_TRY(byte_launch(ctx, nullptr, 0, nullptr, nullptr, 256, nullptr, B, d_idx_x, d_idx_y, (double*)d_hist, BL));
+    return byte_wait(ctx, BL, 0, nullptr, B);
 }
 
 // gd_prebin8_hist2d: gd_prebin8_batch (for the `ncols` stale columns) and gd_hist2d_prebinned8 in ONE stream-ordered
@@ -1989,83 +1918,14 @@ int gd_prebin8_hist2d(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const dou
     if (ctx->w) {  // real weights: the two steps one after the other (the weighted histograms are several launches anyway)
         if (ncols) {
             GD_TRY(gd_prebin8_batch(ctx, cols, ncols, binmin, width, 256, d_idx_out, bad_out));
-            int64_t nbad = 0;
-            for (int c = 0; c < ncols; ++c) nbad += bad_out[c];
-            if (nbad) return gd_fail(ctx, GD_ERR_SOLVER, "%lld samples outside the byte-index grid: use the u16 path", (long long)nbad);
+            GD_TRY(require_inside_grid(ctx, bad_out, ncols));
         }
         return gd_hist2d_prebinned8(ctx, B, d_idx_x, d_idx_y, d_hist);
     }
-    const int F = 256;
-    for (int c = 0; c < ncols; ++c) GD_REQUIRE(cols[c] >= 0 && cols[c] < ctx->n + GD_EXTRA_COLS && d_idx_out[c], "bad column");
-    const BucketRoute R = ncols ? bucket_route(ctx, cols, ncols, binmin, width, d_idx_out) : BucketRoute();
-    std::vector<PrebinCol8> hc;
-    std::vector<int> fp_of((size_t)ncols, -1);
-    for (int c = 0; c < ncols; ++c) {
-        if (R.slot_of[c] >= 0) continue;
-        PrebinCol8 r;
-        r.x = ctx->cols + (int64_t)cols[c] * ctx->ld;
-        r.idx = (unsigned char*)d_idx_out[c];
-        r.binmin = binmin[c];
-        r.width = width[c];
-        fp_of[c] = (int)hc.size();
-        hc.push_back(r);
-    }
-    const int nfp = (int)hc.size();
-    std::vector<Hist2DPair8> hp((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        hp[b].ix = (const unsigned char*)d_idx_x[b];
-        hp[b].iy = (const unsigned char*)d_idx_y[b];
-        GD_REQUIRE(hp[b].ix && hp[b].iy, "null index column");
-    }
-    BucketRouteLayout L(ctx, R);
-    ScratchPlan sp;
-    auto d_c = sp.take<PrebinCol8>(nfp);
-    auto d_pairs = sp.take<Hist2DPair8>(B);
-    const int64_t table_bytes = sp.bytes();  // the two tables go up in one copy
-    auto d_bad = sp.take<unsigned long long>(nfp);
-    auto d_flags = sp.take<int>(B);
-    const int64_t zero_end = sp.bytes();  // the counters and the flags are zeroed in one fill
-    const int nchunks = u8_chunks(ctx, B, ctx->N);
-    auto d_part = sp.take<unsigned int>(nchunks > 1 ? (int64_t)B * nchunks * 32768 : 0);
-    auto d_route = sp.take<char>(L.sp.bytes());
-    GD_TRY(sp.get2(ctx));
-    L.sp.place(d_route);
-    {
-        std::vector<char> tab((size_t)table_bytes, 0);
-        if (nfp) memcpy(tab.data() + d_c.off, hc.data(), (size_t)nfp * sizeof(PrebinCol8));
-        memcpy(tab.data() + d_pairs.off, hp.data(), (size_t)B * sizeof(Hist2DPair8));
-        GD_TRY(gd_stage_h2d(ctx, d_c, tab.data(), (size_t)table_bytes));
-    }
-    GD_HIP(hipMemsetAsync(d_bad, 0, (size_t)(zero_end - d_bad.off), ctx->stream));
-    if (nfp) {
-        int nblk = (int)((ctx->N / 8 + 255) / 256);
-        if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-        if (nblk < 1) nblk = 1;
-        k_prebin8_batch<<<dim3(nblk, nfp), 256, 0, ctx->stream>>>(d_c, ctx->N, F, d_bad);
-        GD_KERNEL_CHECK();
-    }
-    unsigned long long* d_bad_bq = nullptr;
-    if (!R.recs.empty()) GD_TRY(bucket_route_launch<true>(ctx, R, L, F, &d_bad_bq));
-    const int nblocks = (B * nchunks + 7) / 8 * 8;
-    GD_HIP(hipFuncSetAttribute((const void*)k_hist2d_u8_pf<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_HIST_BYTES + 128));
-    k_hist2d_u8_pf<3><<<nblocks, 1024, LDS_HIST_BYTES + 128, ctx->stream>>>(d_pairs, B, ctx->N, (double*)d_hist, d_flags, nchunks, d_part);
-    GD_KERNEL_CHECK();
-    if (nchunks > 1) {
-        k_p8_reduce<<<dim3(32, B), 256, 0, ctx->stream>>>(d_part, nchunks, (double*)d_hist);
-        GD_KERNEL_CHECK();
-    }
-    std::vector<unsigned long long> hb((size_t)nfp), hq(R.recs.size());
-    std::vector<int> hf((size_t)B);
-    if (nfp) GD_TRY(gd_fetch(ctx, hb.data(), d_bad, (size_t)nfp * 8));
-    if (!R.recs.empty()) GD_TRY(gd_fetch(ctx, hq.data(), d_bad_bq, hq.size() * 8));
-    GD_TRY(gd_fetch(ctx, hf.data(), d_flags, (size_t)B * 4));
-    GD_TRY(gd_stream_sync(ctx));
-    int64_t nbad = 0;
-    for (int c = 0; c < ncols; ++c) bad_out[c] = (int64_t)(R.slot_of[c] >= 0 ? hq[R.slot_of[c]] : hb[fp_of[c]]), nbad += bad_out[c];
-    if (nbad) return gd_fail(ctx, GD_ERR_SOLVER, "%lld samples outside the byte-index grid: use the u16 path", (long long)nbad);
-    for (int b = 0; b < B; ++b)
-        if (hf[b]) return gd_fail(ctx, GD_ERR_SOLVER, "16-bit bin counter wrapped in pair %d: redo with gd_hist2d_prebinned", b);
-    return GD_OK;
+    GD_REQUIRE_COLUMNS(cols, ncols);
+    ByteLaunch BL;
+    GD_TRY(byte_launch(ctx, cols, ncols, binmin, width, 256, d_idx_out, B, d_idx_x, d_idx_y, (double*)d_hist, BL));
+    return byte_wait(ctx, BL, ncols, bad_out, B);
 }
 
 int gd_hist2d_sheared(gd_ctx* ctx, int32_t B, const int32_t* coli, const int32_t* colj, const double* r0,
@@ -2073,13 +1933,11 @@ int gd_hist2d_sheared(gd_ctx* ctx, int32_t B, const int32_t* coli, const int32_t
                       int32_t F, void* d_hist) {
     GD_REQUIRE(ctx && coli && colj && r0 && r1 && xmin && dx && ymin && dy && d_hist && B > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
-    std::vector<Hist2DPair> hp((size_t)B);
+    GD_REQUIRE_COLUMNS(coli, B);
+    GD_REQUIRE_COLUMNS(colj, B);
+    std::vector<Hist2DPair> hp = pairs_of_columns(ctx, B, coli, colj);
     for (int b = 0; b < B; ++b) {
-        GD_REQUIRE(coli[b] >= 0 && coli[b] < ctx->n + GD_EXTRA_COLS && colj[b] >= 0 && colj[b] < ctx->n + GD_EXTRA_COLS, "column out of range");
         Hist2DPair& p = hp[b];
-        memset(&p, 0, sizeof p);
-        p.x = ctx->cols + (int64_t)coli[b] * ctx->ld;
-        p.y = ctx->cols + (int64_t)colj[b] * ctx->ld;
         p.bx = xmin[b], p.wx = dx[b], p.by = ymin[b], p.wy = dy[b], p.r0 = r0[b], p.r1 = r1[b];
     }
     return launch_hist2d<1>(ctx, B, hp, F, (double*)d_hist);
@@ -2089,107 +1947,46 @@ int gd_minmax_affine(gd_ctx* ctx, int32_t B, const int32_t* coli, const int32_t*
                      const double* b, double* out) {
     GD_REQUIRE(ctx && coli && colj && a && b && out && B > 0, "bad argument");
     GD_REQUIRE(ctx->cols, "no samples uploaded");
-    std::vector<Hist2DPair> hp((size_t)B);
-    for (int q = 0; q < B; ++q) {
-        GD_REQUIRE(coli[q] >= 0 && coli[q] < ctx->n + GD_EXTRA_COLS && colj[q] >= 0 && colj[q] < ctx->n + GD_EXTRA_COLS, "column out of range");
-        Hist2DPair& p = hp[q];
-        memset(&p, 0, sizeof p);
-        p.x = ctx->cols + (int64_t)coli[q] * ctx->ld;
-        p.y = ctx->cols + (int64_t)colj[q] * ctx->ld;
-        p.r0 = a[q], p.r1 = b[q];
+    GD_REQUIRE_COLUMNS(coli, B);
+    GD_REQUIRE_COLUMNS(colj, B);
+    // groups of pairs over shared columns (each column of a group is read once), or one unit per pair
+    const bool grouped = B >= 4 && getenv("GDHIP_MINMAX_UNGROUPED") == nullptr;
+    std::vector<MinmaxGroup> groups;
+    std::vector<std::vector<int>> members;  // original pair index per slot
+    std::vector<Hist2DPair> hp;
+    if (grouped) {
+        minmax_groups(B, coli, colj, a, b, ctx->cols, ctx->ld, groups, members);
+    } else {
+        hp = pairs_of_columns(ctx, B, coli, colj);
+        for (int q = 0; q < B; ++q) hp[q].r0 = a[q], hp[q].r1 = b[q];
     }
-    if (B >= 4 && getenv("GDHIP_MINMAX_UNGROUPED") == nullptr) {
-        // groups of pairs over shared columns: each column of a group is read once
-        std::vector<int> order((size_t)B);
-        for (int q = 0; q < B; ++q) order[q] = q;
-        std::sort(order.begin(), order.end(), [&](int u, int v) {
-            const int ul = std::min(coli[u], colj[u]), uh = std::max(coli[u], colj[u]);
-            const int vl = std::min(coli[v], colj[v]), vh = std::max(coli[v], colj[v]);
-            return ul != vl ? ul < vl : (uh != vh ? uh < vh : u < v);
-        });
-        std::vector<MinmaxGroup> groups;
-        std::vector<std::vector<int>> members;  // original pair index per slot
-        std::vector<int> gcols;                 // column ids of the open group
-        auto slot_of = [&](int c) {
-            for (size_t k = 0; k < gcols.size(); ++k)
-                if (gcols[k] == c) return (int)k;
-            return -1;
-        };
-        for (int q : order) {
-            const int ci = coli[q], cj = colj[q];
-            bool open = !groups.empty();
-            if (open) {
-                const int need = (slot_of(ci) < 0) + (cj != ci && slot_of(cj) < 0);
-                open = (int)gcols.size() + need <= MMG_COLS && groups.back().npairs < MMG_PAIRS;
-            }
-            if (!open) {
-                MinmaxGroup g;
-                memset(&g, 0, sizeof g);
-                groups.push_back(g);
-                members.emplace_back();
-                gcols.clear();
-            }
-            MinmaxGroup& g = groups.back();
-            for (int c : {ci, cj})
-                if (slot_of(c) < 0) {
-                    g.col[gcols.size()] = ctx->cols + (int64_t)c * ctx->ld;
-                    gcols.push_back(c);
-                }
-            g.ncols = (int)gcols.size();
-            g.a[g.npairs] = slot_of(ci), g.b[g.npairs] = slot_of(cj);
-            g.r0[g.npairs] = a[q], g.r1[g.npairs] = b[q];
-            members.back().push_back(q);
-            ++g.npairs;
-        }
-        const int ng = (int)groups.size();
-        int nblk = (6 * ctx->cu_count + ng - 1) / ng;
-        if (nblk < 8) nblk = 8;
-        if (nblk > 1024) nblk = 1024;
-        const int64_t part_doubles = (int64_t)ng * nblk * MMG_PAIRS * 2;
-        ScratchPlan sp;
-        auto d_groups = sp.take<MinmaxGroup>(ng);
-        auto d_part = sp.tail<double>(part_doubles);
-        GD_TRY(sp.get(ctx));
-        GD_TRY(gd_h2d(ctx, d_groups, groups.data(), (size_t)ng * sizeof(MinmaxGroup)));
-        k_minmax_affine_grouped<<<dim3(nblk, ng), 256, 0, ctx->stream>>>(d_groups, ctx->N, d_part);
-        GD_KERNEL_CHECK();
-        std::vector<double> h((size_t)part_doubles);
-        GD_TRY(gd_fetch(ctx, h.data(), d_part, h.size() * 8));
-        GD_TRY(gd_stream_sync(ctx));
-        for (int g = 0; g < ng; ++g)
-            for (int p = 0; p < groups[g].npairs; ++p) {
-                double mn = INFINITY, mx = -INFINITY;
-                for (int k = 0; k < nblk; ++k) {
-                    const double* v = &h[(((size_t)g * nblk + k) * MMG_PAIRS + p) * 2];
-                    if (v[0] < mn) mn = v[0];
-                    if (v[1] > mx) mx = v[1];
-                }
-                out[2 * members[g][p]] = mn, out[2 * members[g][p] + 1] = mx;
-            }
-        return GD_OK;
-    }
-    int nblk = (4 * ctx->cu_count + B - 1) / B;
-    if (nblk < 8) nblk = 8;
-    if (nblk > 1024) nblk = 1024;
+    const int units = grouped ? (int)groups.size() : B, slots = grouped ? MMG_PAIRS : 1;
+    const int nblk = minmax_blocks(ctx->cu_count, grouped ? 6 : 4, units);
+    const size_t table_bytes = grouped ? (size_t)units * sizeof(MinmaxGroup) : (size_t)units * sizeof(Hist2DPair);
+    std::vector<double> h((size_t)units * nblk * slots * 2);  // (unit, block, slot): min, max
     ScratchPlan sp;
-    auto d_pairs = sp.take<Hist2DPair>(B);
-    auto d_part = sp.tail<double>((int64_t)B * nblk * 2);
+    auto d_table = sp.take<char>((int64_t)table_bytes);
+    auto d_part = sp.tail<double>((int64_t)h.size());
     GD_TRY(sp.get(ctx));
-    GD_TRY(gd_h2d(ctx, d_pairs, hp.data(), (size_t)B * sizeof(Hist2DPair)));
-    k_minmax_affine<<<dim3(nblk, B), 256, 0, ctx->stream>>>(d_pairs, ctx->N, d_part);
+    GD_TRY(gd_h2d(ctx, d_table, grouped ? (const void*)groups.data() : (const void*)hp.data(), table_bytes));
+    if (grouped)
+        k_minmax_affine_grouped<<<dim3(nblk, units), 256, 0, ctx->stream>>>((const MinmaxGroup*)d_table.ptr(), ctx->N, d_part);
+    else
+        k_minmax_affine<<<dim3(nblk, units), 256, 0, ctx->stream>>>((const Hist2DPair*)d_table.ptr(), ctx->N, d_part);
     GD_KERNEL_CHECK();
-    std::vector<double> h((size_t)B * nblk * 2);
     GD_TRY(gd_fetch(ctx, h.data(), d_part, h.size() * 8));
     GD_TRY(gd_stream_sync(ctx));
-    for (int q = 0; q < B; ++q) {
-        double mn = INFINITY, mx = -INFINITY;
-        for (int k = 0; k < nblk; ++k) {
-            const double v0 = h[((size_t)q * nblk + k) * 2], v1 = h[((size_t)q * nblk + k) * 2 + 1];
-            if (v0 < mn) mn = v0;
-            if (v1 > mx) mx = v1;
+    for (int u = 0; u < units; ++u)
+        for (int p = 0; p < (grouped ? groups[u].npairs : 1); ++p) {  // the one fold over a unit's blocks
+            double mn = INFINITY, mx = -INFINITY;
+            for (int k = 0; k < nblk; ++k) {
+                const double* v = &h[(((size_t)u * nblk + k) * slots + p) * 2];
+                if (v[0] < mn) mn = v[0];
+                if (v[1] > mx) mx = v[1];
+            }
+            const int q = grouped ? members[u][p] : u;
+            out[2 * q] = mn, out[2 * q + 1] = mx;
         }
-        out[2 * q] = mn, out[2 * q + 1] = mx;
-    }
     return GD_OK;
 }
 

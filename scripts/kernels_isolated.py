@@ -3,6 +3,8 @@ Isolated kernel timings on the MI355X (HIP events through the C ABI):  python sc
   the O(N) kernels of a C3 step one by one (statistics, quantile select, N_eff lag sums, pre-binning, byte-index binning,
   sheared min/max + re-binning), the optimiser in its two stages with both DCT routes, real-weight and integer-weight 2D
   binning of the whole triangle.  Writes gpurun_out/kernels_isolated.json.
+  --binning: stop behind the binning launches (byte route, an up-scaled class, shear chain), before the optimiser and the
+  weighted sets; --out FILE: write there instead.
 """
 import json
 import os
@@ -29,7 +31,14 @@ def timed(ctx, fn, reps=5):
     return round(float(np.median(ms)), 4)
 
 
+def finish(res, path):
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    json.dump(res, open(path, "w"), indent=1)
+    print(json.dumps(res, indent=1))
+
+
 def main():
+    out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(OUT, "kernels_isolated.json")
     res = {}
     N, n, F = 10_000_000, 50, 256
     s, w, names, ranges = synth.config_c3(N, n)
@@ -66,6 +75,11 @@ def main():
     os.environ["GDHIP_NO_BUCKET_COLS"] = "1"
     res["prebin_u16_12_columns_F960_from_fp64_samples"] = timed(ctx, lambda: ctx.prebin_batch(cols[:12], [x[1] for x in e960], [x[0] for x in e960], 960, b16))
     os.environ.pop("GDHIP_NO_BUCKET_COLS")
+    # an up-scaled grid class: a dozen pairs of u16 index columns at F = 960 (packed counters over pair x chunk x stripe)
+    up = [(a, b) for a in range(12) for b in range(a)][:12]
+    d_up = ctx.alloc(len(up) * 960 * 960 * 8)
+    res["hist2d_prebinned_u16_%d_pairs_F960" % len(up)] = timed(ctx, lambda: ctx.hist2d_prebinned([b16[a] for a, b in up], [b16[b] for a, b in up], 960, out=d_up))
+    d_up.free()
     for b in b16:
         b.free()
     pairs = [p for p in synth.triangle_pairs(n) if abs(corr[p[1]][p[0]]) <= 0.866]
@@ -84,6 +98,9 @@ def main():
     dy = (m2[:, 1] + 0.1 - ymin) / (F - 1)
     d_rot = ctx.alloc(len(A) * F * F * 8)
     res["hist2d_sheared_%d_pairs" % len(A)] = timed(ctx, lambda: ctx.hist2d_sheared(ci, cj, r0, r1, xmin, dx, ymin, dy, F, out=d_rot))
+    if "--binning" in sys.argv:
+        mc.ctx.close()
+        return finish(res, out_path)
     # the optimiser on the triangle's own histograms: whole call, both DCT routes
     B = len(pairs)
     neff = np.full(B, float(N))
@@ -121,9 +138,7 @@ def main():
             res["hist2d_byte_index_real_weights_sorted_by_stripe_%d_pairs" % len(allp)] = timed(
                 mc2.ctx, lambda: mc2.ctx.hist2d_prebinned8([b8[a] for a, b in allp], [b8[b] for a, b in allp], out=o2), 3)
         mc2.ctx.close()
-    os.makedirs(OUT, exist_ok=True)
-    json.dump(res, open(os.path.join(OUT, "kernels_isolated.json"), "w"), indent=1)
-    print(json.dumps(res, indent=1))
+    finish(res, out_path)
 
 
 if __name__ == "__main__":

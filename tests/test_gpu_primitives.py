@@ -255,6 +255,32 @@ def test_hist2d_u16_counters_overflow_is_detected_and_redone(ctx):
     assert max(H[k].max() for k in range(len(pairs))) > 65535
 
 
+@pytest.mark.parametrize("F", [384, 256])
+def test_hist2d_prebinned_chunk_route_redoes_wrapped_pairs(ctx, monkeypatch, F):
+    """Few pairs of pre-binned u16 columns (an up-scaled grid class) take the packed-counter kernel over (pair, chunk of
+    rows, stripe) blocks.  N = 200 003 rows are cut into three chunks of 66 672 / 66 672 / 66 659 (pick_chunks for 2 pairs on
+    a chip of >= 64 CUs; tests/native/binplan_check.cpp pins the three): with a constant y column every chunk puts more than
+    65 535 samples into one row of bins -- all into ONE bin for the (constant, constant) pair -- so every chunk's 16-bit
+    counter wraps and the pair must come back from the 32-bit redo, exact."""
+    r = np.random.default_rng(11)
+    N = 200_003
+    s = np.column_stack([np.full(N, 0.5), np.full(N, 0.25), r.random(N)])
+    ctx.upload(s, None)
+    org, width = -0.001, 1.002 / (F - 1)
+    pre = [ctx.prebin(c, org, width, F) for c in range(3)]
+    idx = [((s[:, c] - org) / width + 0.5).astype(int) for c in range(3)]
+    pairs = [(0, 1), (2, 1)]  # (constant, constant) and (uniform, constant)
+    H = ctx.hist2d_prebinned([pre[a] for a, b in pairs], [pre[b] for a, b in pairs], F).to_host((len(pairs), F, F))
+    for k, (a, b) in enumerate(pairs):
+        ref = np.bincount(idx[a] + idx[b] * F, minlength=F * F).reshape(F, F)
+        assert np.array_equal(H[k], ref), (F, a, b, H[k].max(), ref.max())
+    assert H.max() == H[0].max() == N  # one bin holds every sample: 3.05 times what a 16-bit counter can
+    assert H[1].sum() == N and H[1].max() < 65535  # (the uniform pair wraps no counter: it is not redone)
+    monkeypatch.setenv("GDHIP_NO_U16_CHUNKS", "1")  # the 32-bit stripe kernel for every pair: the same grids bit for bit
+    H32 = ctx.hist2d_prebinned([pre[a] for a, b in pairs], [pre[b] for a, b in pairs], F).to_host((len(pairs), F, F))
+    assert np.array_equal(H32, H)
+
+
 def test_integer_weights_take_exact_u32_path(ctx):
     """MCMC multiplicities: integral weights use u32 LDS counters (2 stripes) and must be bit-exact."""
     r = np.random.default_rng(7)
