@@ -1,6 +1,7 @@
 // Weighted moments, covariance, sort-free weighted quantiles, autocovariance lags, Gaussian-kernel lag sums.
 // All streaming kernels read the SoA columns with 16-byte (double2) loads, coalesced across the wave.
 #include "ctx.hpp"
+#include "statsplan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -242,8 +243,6 @@ __global__ void k_col_fin2(const double* __restrict__ part, int nblk, const doub
 // ---- weighted covariance (two-pass) -----------------------------------------------------------------------
 // One block = one 64x64 tile of column pairs over one chunk of rows; 256 threads = 4 waves of 32x32 outputs on the
 // fp64 matrix cores.
-#define CT 64
-#define CRB 64
 template <bool HAS_W>
 __global__ void __launch_bounds__(256) k_cov_tile(const double* __restrict__ cols, int64_t ld,
                                                   const int32_t* __restrict__ colidx, int m,
@@ -976,8 +975,6 @@ __global__ void __launch_bounds__(1024) k_qsel_finish(const QState* __restrict__
 // bucket of a few hundred to a few thousand rows; the collect pass and k_qsel_finish (sorted walk of the cumulative
 // weight, chains.py:807-838) are those of the radix path.  The radix path's first digit is sign + exponent, which
 // separates nothing for data of one magnitude: that is why it needs three passes before the collect.
-#define QLIN_NB_U 32768
-#define QLIN_NB_W 16384
 struct QLin {  // per column, next to its QState
     double mn, scale;
     int nb, pad;
@@ -1532,7 +1529,6 @@ __device__ __forceinline__ double exp_neg(double t, const double* __restrict__ t
     return __builtin_ldexp(tab[m & 63] * p, m >> 6);
 }
 
-#define KDE_LAG_MAX 8
 // All NL lags of a column in one read: grid (blocks, columns), rows in chunks of 256.  Chunks below min(N - k) need no
 // bounds handling at all (straight-line code: NL loads in flight, NL interleaved exponentials); the others skip a lag
 // whose range has ended for the whole chunk (with lags near N/2 that is most of the second half) and mask the rest.
@@ -1764,6 +1760,31 @@ __global__ void k_kde_lag_2d(const double* __restrict__ x, const double* __restr
 }
 
 // =============================================================================================================
+// Host side.  Block counts, the covariance route and configuration, the quantile route and the shape of a lag set come from
+// statsplan.hpp.
+
+// partial sums of one group, `stride` doubles apart, added in block order
+static double sum_blocks(const double* h, int nblk, size_t stride = 1) {
+    double sum = 0;
+    for (int b = 0; b < nblk; ++b) sum += h[(size_t)b * stride];
+    return sum;
+}
+// out[g] = group g's nblk partial sums (part: groups x nblk) fetched and added in block order
+static int fetch_group_sums(gd_ctx* ctx, const double* part, size_t groups, int nblk, double* out) {
+    std::vector<double> h(groups * nblk);
+    GD_TRY(gd_fetch(ctx, h.data(), part, h.size() * 8));
+    GD_TRY(gd_stream_sync(ctx));
+    for (size_t g = 0; g < groups; ++g) out[g] = sum_blocks(&h[g * nblk], nblk);
+    return GD_OK;
+}
+// f(std::integral_constant<int, pick>): one instantiation of f per row of COV_CFGS
+template <int I = 0, class F>
+static int cov_by_cfg(int pick, F&& f) {
+    if constexpr (I + 1 < COV_NCFG)
+        if (pick != I) return cov_by_cfg<I + 1>(pick, f);
+    return f(std::integral_constant<int, I>{});
+}
+
 extern "C" {
 
 int gd_kde_lag_sums_2d(gd_ctx* ctx, int32_t coli, int32_t colj, const double* kinv3, const int64_t* lags, int32_t nlags,
@@ -1771,9 +1792,7 @@ int gd_kde_lag_sums_2d(gd_ctx* ctx, int32_t coli, int32_t colj, const double* ki
     GD_REQUIRE(ctx && kinv3 && lags && out && nlags > 0 && nlags <= 64, "bad argument");
     GD_REQUIRE(ctx->cols && coli >= 0 && coli < ctx->n + GD_EXTRA_COLS && colj >= 0 && colj < ctx->n + GD_EXTRA_COLS, "bad column");
     for (int i = 0; i < nlags; ++i) GD_REQUIRE(lags[i] > 0 && lags[i] < ctx->N, "lag out of range");
-    int nblk = (8 * ctx->cu_count + nlags - 1) / nlags;
-    if (nblk < 8) nblk = 8;
-    if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
+    const int nblk = group_blocks(ctx->cu_count, nlags);
     ScratchPlan sp;
     auto part = sp.take<double>((int64_t)nlags * nblk);
     auto d_lags = sp.tail<int64_t>(nlags);
@@ -1787,15 +1806,7 @@ int gd_kde_lag_sums_2d(gd_ctx* ctx, int32_t coli, int32_t colj, const double* ki
         k_kde_lag_2d<HW.value><<<grid, 256, 0, ctx->stream>>>(x, y, ctx->w, ctx->N, kinv3[0], kinv3[1], kinv3[2], d_lags, part);
     });
     GD_KERNEL_CHECK();
-    std::vector<double> h((size_t)nlags * nblk);
-    GD_TRY(gd_fetch(ctx, h.data(), part, h.size() * 8));
-    GD_TRY(gd_stream_sync(ctx));
-    for (int l = 0; l < nlags; ++l) {
-        double sum = 0;
-        for (int b = 0; b < nblk; ++b) sum += h[(size_t)l * nblk + b];
-        out[l] = sum;
-    }
-    return GD_OK;
+    return fetch_group_sums(ctx, part, (size_t)nlags, nblk, out);
 }
 
 int gd_weight_stats(gd_ctx* ctx, int64_t lo, int64_t hi, double thresh, double* out4) {
@@ -1904,134 +1915,62 @@ int gd_cov(gd_ctx* ctx, const int32_t* cols, int32_t m, int64_t lo, int64_t hi, 
     GD_REQUIRE_ROWS(lo, hi);
     GD_REQUIRE_COLUMNS(cols, m);
     const int64_t rows = hi - lo;
-    double* d_res = nullptr;
-    double* d_cov = nullptr;
-    const bool slab = (m <= 208) && !getenv("GDHIP_COV_TILE");
+    const bool hw = ctx->w != nullptr;
+    const CovSlabPlan sl = cov_slab_plan(m, rows, ctx->cu_count, hw, getenv("GDHIP_COV_TWOPASS") != nullptr);
+    const bool slab = sl.route != COV_TILE, onepass = sl.route == COV_ONEPASS;
+    GD_REQUIRE(!slab || sl.pick >= 0, "covariance: no slab configuration");
+    CovTilePlan tl;
+    if (!slab) tl = cov_tile_plan(m, rows, ctx->cu_count);
+    const int ntp = (int)tl.tiles.size();
+    static_assert(sizeof(CovTile) == sizeof(int2), "the kernels read the tile list as int2");
+    // the partial tables: per (block, 16 x 16 tile pair) of the slab kernel, per (tile, chunk) of the tile kernel
+    ScratchPlan sp;
+    auto d_part1 = sp.take<double>((int64_t)m * NBLK_STREAM * 4);
+    auto d_res = sp.take<double>((int64_t)m * 4);
+    auto d_idx = sp.take<int32_t>(m);
+    auto d_tiles = sp.take<int2>(ntp);
+    auto d_cpart = sp.take<double>(slab ? (int64_t)sl.nblk * sl.T * 256 : (int64_t)ntp * tl.nchunks * CT * CT);
+    auto d_cov = sp.take<double>((int64_t)m * m);
+    auto d_mm = sp.take<double>(slab ? (int64_t)sl.nblk * m * 2 : 0);
+    auto d_S = sp.take<double>(slab ? (int64_t)sl.mc * sl.mc : 0);
+    GD_TRY(sp.get(ctx));
+    GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)m * 4));
+    GD_TRY(gd_h2d(ctx, d_tiles, tl.tiles.data(), (size_t)ntp * 8));
+    if (onepass) {
+        k_col_shift<<<m, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, lo, hi, d_res);
+        GD_KERNEL_CHECK();
+    } else
+        GD_TRY(col_stats_device(ctx, d_idx, m, lo, hi, d_res, d_part1, nullptr));
     if (slab) {
-        // one pass (round 6): no means pass in front -- a provisional shift, the ones column, k_cov_onepass_fin (above
-        // k_cov_slab2).  m = 208 has no room for the extra column and keeps the two passes.
-        const bool onepass = m + 1 <= 208 && !getenv("GDHIP_COV_TWOPASS");
-        const int me = onepass ? m + 1 : m;
-        // ---- slab kernel: pick the wave arrangement with the fewest tile-pair slots >= T
-        const int nt16 = (me + 15) / 16, T = nt16 * (nt16 + 1) / 2, mc = nt16 * 16;
-        const int KS = mc <= 64 ? 64 : 32;  // narrow matrices: more rows per barrier pair
-        struct Cfg { int mcap, nw, nh, p, bpc; };
-        static const Cfg cfgs[] = {{64, 8, 8, 3, 4},  {64, 8, 4, 3, 4},   {64, 8, 4, 5, 4},   {112, 8, 2, 4, 2}, {112, 8, 2, 6, 2},
-                                   {112, 8, 2, 7, 2}, {208, 16, 2, 6, 1}, {208, 16, 1, 5, 1}, {208, 16, 1, 6, 1}};
-        int pick = -1;
-        for (int k = 0; k < (int)(sizeof(cfgs) / sizeof(cfgs[0])); ++k)
-            if (cfgs[k].mcap >= mc && (cfgs[k].nw / cfgs[k].nh) * cfgs[k].p >= T) {
-                pick = k;
-                break;
-            }
-        GD_REQUIRE(pick >= 0, "covariance: no slab configuration");
-        const Cfg cf = cfgs[pick];
-        const bool hw = ctx->w != nullptr;
-        size_t lds = (size_t)(hw ? 2 : 1) * mc * (KS + 2) * 8 + (onepass ? (size_t)mc * 8 : 0);
-        if (cf.nh > 1) lds = std::max(lds, (size_t)(cf.nw / cf.nh) * cf.p * 256 * 8);  // the in-block sum over the row-splits
-        int bpc = cf.bpc;
-        while (bpc > 1 && (size_t)bpc * lds > 150u * 1024u) --bpc;
-        int nblk = bpc * ctx->cu_count;
-        if (nblk > (rows + 4 * KS - 1) / (4 * KS)) nblk = (int)((rows + 4 * KS - 1) / (4 * KS));
-        if (nblk < 1) nblk = 1;
-        int64_t rows_per_chunk = (rows + nblk - 1) / nblk;
-        rows_per_chunk = (rows_per_chunk + KS - 1) / KS * KS;
-        nblk = (int)((rows + rows_per_chunk - 1) / rows_per_chunk);
-        ScratchPlan sp;
-        auto d_part1 = sp.take<double>((int64_t)m * NBLK_STREAM * 4);
-        auto b_res = sp.take<double>((int64_t)m * 4);
-        auto d_idx = sp.take<int32_t>(m);
-        auto d_cpart = sp.take<double>((int64_t)nblk * T * 256);
-        auto b_cov = sp.take<double>((int64_t)m * m);
-        auto d_mm = sp.take<double>((int64_t)nblk * m * 2);
-        auto d_S = sp.take<double>((int64_t)mc * mc);
-        GD_TRY(sp.get(ctx));
-        d_res = b_res, d_cov = b_cov;
-        GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)m * 4));
-        if (onepass) {
-            k_col_shift<<<m, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, lo, hi, d_res);
-            GD_KERNEL_CHECK();
-        } else {
-            int rc = col_stats_device(ctx, d_idx, m, lo, hi, d_res, d_part1, nullptr);
-            if (rc) return rc;
-        }
-#define GD_COV2(HW, MCAP, NW, NH, PP)                                                                                     \
-    do {                                                                                                                  \
-        if (onepass) {                                                                                                    \
-            auto kern = k_cov_slab2<HW, MCAP, NW, NH, PP, ((MCAP) <= 64 ? 64 : 32), ((MCAP) <= 64 ? 2 : 1), true>;        \
-            GD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
-            kern<<<nblk, (NW) * 64, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, ctx->w, lo, hi, rows_per_chunk, \
-                                                        d_cpart, d_mm);                                                   \
-        } else {                                                                                                          \
-            auto kern = k_cov_slab2<HW, MCAP, NW, NH, PP, ((MCAP) <= 64 ? 64 : 32), ((MCAP) <= 64 ? 2 : 1), false>;       \
-            GD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
-            kern<<<nblk, (NW) * 64, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, ctx->w, lo, hi, rows_per_chunk, \
-                                                        d_cpart, nullptr);                                                \
-        }                                                                                                                 \
-    } while (0)
-#define GD_COV2_HW(MCAP, NW, NH, PP) \
-    do {                              \
-        if (hw)                       \
-            GD_COV2(true, MCAP, NW, NH, PP);  \
-        else                          \
-            GD_COV2(false, MCAP, NW, NH, PP); \
-    } while (0)
-        switch (pick) {
-            case 0: GD_COV2_HW(64, 8, 8, 3); break;
-            case 1: GD_COV2_HW(64, 8, 4, 3); break;
-            case 2: GD_COV2_HW(64, 8, 4, 5); break;
-            case 3: GD_COV2_HW(112, 8, 2, 4); break;
-            case 4: GD_COV2_HW(112, 8, 2, 6); break;
-            case 5: GD_COV2_HW(112, 8, 2, 7); break;
-            case 6: GD_COV2_HW(208, 16, 2, 6); break;
-            case 7: GD_COV2_HW(208, 16, 1, 5); break;
-            default: GD_COV2_HW(208, 16, 1, 6); break;
-        }
-#undef GD_COV2_HW
-#undef GD_COV2
+        GD_TRY(cov_by_cfg(sl.pick, [&](auto I) -> int {
+            return gd_by_flag(hw, [&](auto HW) -> int {
+                return gd_by_flag(onepass, [&](auto OP) -> int {
+                    constexpr CovCfg cf = COV_CFGS[decltype(I)::value];
+                    auto kern = k_cov_slab2<HW.value, cf.mcap, cf.nw, cf.nh, cf.p, cov_ks(cf.mcap), cov_depth(cf.mcap), OP.value>;
+                    GD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl.lds));
+                    kern<<<sl.nblk, cf.nw * 64, sl.lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, ctx->w, lo, hi, sl.rows_per_chunk,
+                                                                      d_cpart, OP.value ? d_mm.ptr() : nullptr);
+                    return GD_OK;
+                });
+            });
+        }));
         GD_KERNEL_CHECK();
         if (onepass) {
-            k_cov_slab_sum<<<T, 1024, 0, ctx->stream>>>(d_cpart, nblk, nt16, d_S);
+            k_cov_slab_sum<<<sl.T, 1024, 0, ctx->stream>>>(d_cpart, sl.nblk, sl.nt16, d_S);
             GD_KERNEL_CHECK();
-            k_cov_onepass_fin<<<m, 256, 0, ctx->stream>>>(d_S, mc, m, d_mm, nblk, d_res, d_cov);
+            k_cov_onepass_fin<<<m, 256, 0, ctx->stream>>>(d_S, sl.mc, m, d_mm, sl.nblk, d_res, d_cov);
         } else {
-            k_cov_slab_fin<<<T, 1024, 0, ctx->stream>>>(d_cpart, nblk, m, d_res, d_cov);
+            k_cov_slab_fin<<<sl.T, 1024, 0, ctx->stream>>>(d_cpart, sl.nblk, m, d_res, d_cov);
         }
         GD_KERNEL_CHECK();
     } else {
-    const int nt = (m + CT - 1) / CT;
-    std::vector<int2> tiles;
-    for (int a = 0; a < nt; ++a)
-        for (int b = a; b < nt; ++b) tiles.push_back(make_int2(a, b));
-    const int ntp = (int)tiles.size();
-    int nchunks = (2 * ctx->cu_count + ntp - 1) / ntp;
-    if (nchunks > (rows + CRB - 1) / CRB) nchunks = (int)((rows + CRB - 1) / CRB);
-    if (nchunks < 1) nchunks = 1;
-    int64_t rows_per_chunk = (rows + nchunks - 1) / nchunks;
-    rows_per_chunk = (rows_per_chunk + CRB - 1) / CRB * CRB;
-    nchunks = (int)((rows + rows_per_chunk - 1) / rows_per_chunk);
-    // scratch layout
-    ScratchPlan sp;
-    auto d_part1 = sp.take<double>((int64_t)m * NBLK_STREAM * 4);
-    auto b_res = sp.take<double>((int64_t)m * 4);
-    auto d_idx = sp.take<int32_t>(m);
-    auto d_tiles = sp.take<int2>(ntp);
-    auto d_cpart = sp.take<double>((int64_t)ntp * nchunks * CT * CT);
-    auto b_cov = sp.take<double>((int64_t)m * m);
-    GD_TRY(sp.get(ctx));
-    d_res = b_res, d_cov = b_cov;
-    GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)m * 4));
-    GD_TRY(gd_h2d(ctx, d_tiles, tiles.data(), (size_t)ntp * 8));
-    int rc = col_stats_device(ctx, d_idx, m, lo, hi, d_res, d_part1, nullptr);
-    if (rc) return rc;
-    dim3 grid(nchunks, ntp);
-    gd_by_flag(ctx->w != nullptr, [&](auto HW) {
-        k_cov_tile<HW.value><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, ctx->w, lo, hi, rows_per_chunk, d_tiles,
-                                                            d_cpart);
-    });
-    GD_KERNEL_CHECK();
-    k_cov_fin<<<dim3((CT * CT + 255) / 256, ntp), 256, 0, ctx->stream>>>(d_cpart, nchunks, d_tiles, m, d_res, d_cov);
-    GD_KERNEL_CHECK();
+        gd_by_flag(hw, [&](auto HW) {
+            k_cov_tile<HW.value><<<dim3(tl.nchunks, ntp), 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, m, d_res, ctx->w, lo, hi,
+                                                                                 tl.rows_per_chunk, d_tiles, d_cpart);
+        });
+        GD_KERNEL_CHECK();
+        k_cov_fin<<<dim3((CT * CT + 255) / 256, ntp), 256, 0, ctx->stream>>>(d_cpart, tl.nchunks, d_tiles, m, d_res, d_cov);
+        GD_KERNEL_CHECK();
     }
     std::vector<double> hres((size_t)m * 4);
     GD_TRY(gd_fetch(ctx, hres.data(), d_res, hres.size() * 8));
@@ -2044,7 +1983,6 @@ int gd_cov(gd_ctx* ctx, const int32_t* cols, int32_t m, int64_t lo, int64_t hi, 
     return GD_OK;
 }
 
-// the linear-bucket path of gd_quantiles_mm; returns 1 when a bucket list overflowed (the caller takes the radix path)
 // Bucket columns of the resident sample set (ctx.hpp BucketCols): allocated on first use when the device has room for them
 // beside what a large call needs (they are an optimisation: without them the later passes read the fp64 samples).
 static unsigned short* bucket_columns(gd_ctx* ctx) {
@@ -2068,64 +2006,73 @@ static unsigned short* bucket_columns(gd_ctx* ctx) {
     return B.buf;
 }
 
-static int quantiles_linear(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, int64_t hi, const double* targets,
-                            int32_t k, const double* minmax, double* out, int* overflowed, const double* probe_means,
-                            double* probe_out) {
-    const bool hw = ctx->w != nullptr;
-    const int nb = hw ? QLIN_NB_W : QLIN_NB_U;
+// ---- what the two quantile routes share: the head of their scratch block, the upload in front, the sorted walk behind
+struct QselScratch {
+    ScratchPlan::Buf<QState> st;
+    ScratchPlan::Buf<int32_t> idx;
+    ScratchPlan::Buf<double> out;
+    ScratchPlan::Buf<int> cnt;  // the overflow flag sits behind the counters
+    ScratchPlan::Buf<unsigned long long> lk;
+    ScratchPlan::Buf<double> lw;
+    QselScratch(ScratchPlan& sp, int ncols, int k)
+        : st(sp.take<QState>(ncols)), idx(sp.take<int32_t>(ncols)), out(sp.take<double>((int64_t)ncols * k)),
+          cnt(sp.take<int>((int64_t)ncols * QK_MAX + 64)), lk(sp.take<unsigned long long>((int64_t)ncols * QK_MAX * QCAP)),
+          lw(sp.take<double>((int64_t)ncols * QK_MAX * QCAP)) {}
+};
+// a fresh QState per column with its targets, the column indices, the list counters and the overflow flag zeroed
+static int qsel_begin(gd_ctx* ctx, const QselScratch& S, const int32_t* cols, int ncols, const double* targets, int k) {
     std::vector<QState> hst((size_t)ncols);
-    std::vector<QLin> hql((size_t)ncols);
     memset(hst.data(), 0, hst.size() * sizeof(QState));
-    memset(hql.data(), 0, hql.size() * sizeof(QLin));
     for (int c = 0; c < ncols; ++c) {
         hst[c].k = k;
         hst[c].nuniq = 1;
         for (int t = 0; t < k; ++t) hst[c].target[t] = targets[(size_t)c * k + t];
+    }
+    GD_TRY(gd_h2d(ctx, S.st, hst.data(), hst.size() * sizeof(QState)));
+    GD_TRY(gd_h2d(ctx, S.idx, cols, (size_t)ncols * 4));
+    GD_HIP(hipMemsetAsync(S.cnt, 0, (size_t)ncols * QK_MAX * 4 + 256, ctx->stream));
+    return GD_OK;
+}
+// The collected lists sorted and walked (`passes` = the radix passes done before the collect; 8 = whole keys, the linear
+// route), then the overflow word, the quantiles and one more array of the caller's fetched.  Real weights walk a list
+// (`unit` = 0), unit weights index it (1).
+static int qsel_finish(gd_ctx* ctx, const QselScratch& S, int ncols, int k, int passes, double* out, int* overflow,
+                       void* also_dst = nullptr, const void* also_src = nullptr, size_t also_bytes = 0) {
+    int* d_overflow = S.cnt + (int64_t)ncols * QK_MAX;
+    k_qsel_finish<<<dim3(ncols, QK_MAX), 1024, 0, ctx->stream>>>(S.st, S.lk, S.lw, S.cnt, k, passes, S.out, d_overflow, ctx->w ? 0 : 1);
+    GD_KERNEL_CHECK();
+    GD_TRY(gd_fetch(ctx, overflow, d_overflow, 4));
+    GD_TRY(gd_fetch(ctx, out, S.out, (size_t)ncols * k * 8));
+    GD_TRY(gd_fetch(ctx, also_dst, also_src, also_bytes));
+    GD_TRY(gd_stream_sync(ctx));
+    return GD_OK;
+}
+
+// The linear-bucket route; *overflowed = 1 when a bucket list overflowed (the caller takes the radix route).  `whole`: every
+// column is one of the sample set's own and the rows are all of them, which takes the fused pass (tiles; bucket columns for
+// the later passes; with probe_means / probe_out the lag probe).
+static int quantiles_linear(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, int64_t hi, const double* targets,
+                            int32_t k, const double* minmax, double* out, int* overflowed, bool whole, const double* probe_means,
+                            double* probe_out) {
+    const bool hw = ctx->w != nullptr;
+    const int nb = hw ? QLIN_NB_W : QLIN_NB_U;
+    std::vector<QLin> hql((size_t)ncols);
+    memset(hql.data(), 0, hql.size() * sizeof(QLin));
+    for (int c = 0; c < ncols; ++c) {
         hql[c].mn = minmax[2 * c];
         hql[c].scale = (double)nb / (minmax[2 * c + 1] - minmax[2 * c]);
         hql[c].nb = nb;
     }
-    // blocks per column: the chip filled about twice over, but every block keeps at least 256K rows to spread its 128-KB
-    // table's zero-fill and flush over (few columns -- one rank's share of the parameters -- would otherwise get 64
-    // blocks of 150K rows each)
-    int nblk = (2 * ctx->cu_count + ncols - 1) / ncols;
-    if (nblk > 32) nblk = 32;
-    if ((int64_t)nblk * 262144 > hi - lo) nblk = (int)((hi - lo + 262143) / 262144);
-    if (nblk < 1) nblk = 1;
-    {
-        // one block per CU (the table is 128 KB): ncols * nblk blocks run in ceil(blocks / CUs) rounds, so a count just
-        // above a multiple of the CU number wastes most of a round (50 columns x 11 blocks = 2.15 rounds took the time of
-        // 3; x 10 = 1.95 rounds: 1.40 -> 1.05 ms).  Among the counts down to half of the first choice take the one that
-        // fills its rounds best.
-        int best = nblk;
-        double best_eff = 0;
-        for (int q = nblk; q >= (nblk + 1) / 2 && q >= 1; --q) {
-            const double rounds = (double)ncols * q / ctx->cu_count;
-            const double eff = rounds / ceil(rounds);
-            if (eff > best_eff + 0.02) best_eff = eff, best = q;
-        }
-        nblk = best;
-    }
-    int nblk2 = (8 * ctx->cu_count + ncols - 1) / ncols;
-    if (nblk2 < 8) nblk2 = 8;
-    if (nblk2 > 2 * ctx->cu_count) nblk2 = 2 * ctx->cu_count;
+    const int nblk = qlin_count_blocks(ctx->cu_count, ncols, hi - lo), nblk2 = qsel_blocks(ctx->cu_count, ncols);
     ScratchPlan sp;
-    auto d_st = sp.take<QState>(ncols);
+    const QselScratch S(sp, ncols, k);
     auto d_ql = sp.take<QLin>(ncols);
-    auto d_idx = sp.take<int32_t>(ncols);
-    auto d_out = sp.take<double>((int64_t)ncols * k);
-    auto d_cnt = sp.take<int>((int64_t)ncols * QK_MAX + 64);  // the overflow flag sits behind the counters
-    auto d_lk = sp.take<unsigned long long>((int64_t)ncols * QK_MAX * QCAP);
-    auto d_lw = sp.take<double>((int64_t)ncols * QK_MAX * QCAP);
     auto d_part = sp.take<char>((int64_t)ncols * nblk * nb * (hw ? 8 : 4));
     auto d_tot = sp.take<double>((int64_t)ncols * nb);
     auto d_pmean = sp.take<double>(ncols);
     auto d_ppart = sp.take<double>((int64_t)ncols * nblk * QP_LAGS);
     auto d_pout = sp.take<double>((int64_t)ncols * QP_LAGS);
     GD_TRY(sp.get(ctx));
-    // whole columns of the sample set: the fused pass (tiles; bucket columns for the later passes; the lag probe on request)
-    bool whole = lo == 0 && hi == ctx->N && !getenv("GDHIP_QLIN_UNFUSED");
-    for (int c = 0; whole && c < ncols; ++c) whole = cols[c] < ctx->n;
     unsigned short* bq = whole ? bucket_columns(ctx) : nullptr;
     const bool probe = whole && probe_means && probe_out;
     if (probe) GD_TRY(gd_h2d(ctx, d_pmean, probe_means, (size_t)ncols * 8));
@@ -2133,10 +2080,8 @@ static int quantiles_linear(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int
         std::lock_guard<std::mutex> g(ctx->bq->mu);
         for (int c = 0; c < ncols; ++c) ctx->bq->nb[cols[c]] = 0;
     }
-    GD_TRY(gd_h2d(ctx, d_st, hst.data(), hst.size() * sizeof(QState)));
+    GD_TRY(qsel_begin(ctx, S, cols, ncols, targets, k));
     GD_TRY(gd_h2d(ctx, d_ql, hql.data(), hql.size() * sizeof(QLin)));
-    GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
-    GD_HIP(hipMemsetAsync(d_cnt, 0, (size_t)ncols * QK_MAX * 4 + 256, ctx->stream));
     const size_t lds = (size_t)nb * (hw ? 8 : 4);
     const size_t lds_tiles = lds + (probe ? (size_t)16 * (128 + QP_LAGS) * 8 : 0);
     // 2^k with 2^k * (sum of all weights) < 2^62 (gd_quantiles_mm checked that the sum is known and positive)
@@ -2147,13 +2092,13 @@ static int quantiles_linear(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int
                 GD_HIP(hipFuncSetAttribute((const void*)k_qlin_count_tiles<HW.value, PROBE.value>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds_tiles));
                 k_qlin_count_tiles<HW.value, PROBE.value><<<dim3(nblk, ncols), 1024, lds_tiles, ctx->stream>>>(
-                    ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_ql, d_part, wscale, bq, PROBE.value ? d_pmean.ptr() : nullptr,
+                    ctx->cols, ctx->ld, S.idx, ctx->w, ctx->N, d_ql, d_part, wscale, bq, PROBE.value ? d_pmean.ptr() : nullptr,
                     PROBE.value ? d_ppart.ptr() : nullptr);
                 return GD_OK;
             }));
         } else {
             GD_HIP(hipFuncSetAttribute((const void*)k_qlin_count<HW.value>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            k_qlin_count<HW.value><<<dim3(nblk, ncols), 1024, lds, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, d_ql, d_part, wscale);
+            k_qlin_count<HW.value><<<dim3(nblk, ncols), 1024, lds, ctx->stream>>>(ctx->cols, ctx->ld, S.idx, ctx->w, lo, hi, d_ql, d_part, wscale);
         }
         GD_KERNEL_CHECK();
         if (probe) {
@@ -2162,31 +2107,23 @@ static int quantiles_linear(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int
         }
         k_qlin_reduce<HW.value><<<dim3(nb / 256, ncols), 256, 0, ctx->stream>>>(d_part, nblk, d_tot, 1.0 / wscale);
         GD_KERNEL_CHECK();
-        k_qlin_scan<HW.value><<<ncols, 1024, 0, ctx->stream>>>(d_st, d_ql, d_tot);
+        k_qlin_scan<HW.value><<<ncols, 1024, 0, ctx->stream>>>(S.st, d_ql, d_tot);
         GD_KERNEL_CHECK();
         if (bq)
-            k_qlin_collect_bq<HW.value><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_st, d_ql, bq, d_lk,
-                                                                                     d_lw, d_cnt);
+            k_qlin_collect_bq<HW.value><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, S.idx, ctx->w, ctx->N, S.st, d_ql, bq, S.lk,
+                                                                                     S.lw, S.cnt);
         else
-            k_qlin_collect<HW.value><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, d_st, d_ql, d_lk, d_lw,
-                                                                                  d_cnt);
+            k_qlin_collect<HW.value><<<dim3(nblk2, ncols), 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, S.idx, ctx->w, lo, hi, S.st, d_ql, S.lk, S.lw,
+                                                                                  S.cnt);
         return GD_OK;
     }));
     GD_KERNEL_CHECK();
-    k_qsel_finish<<<dim3(ncols, QK_MAX), 1024, 0, ctx->stream>>>(d_st, d_lk, d_lw, d_cnt, k, 8, d_out, d_cnt + (int64_t)ncols * QK_MAX,
-                                                                 hw || getenv("GDHIP_QSEL_WALK") ? 0 : 1);
-    GD_KERNEL_CHECK();
-    int overflow = 0;
-    GD_TRY(gd_fetch(ctx, &overflow, d_cnt + (int64_t)ncols * QK_MAX, 4));
-    GD_TRY(gd_fetch(ctx, out, d_out, (size_t)ncols * k * 8));
-    if (probe) GD_TRY(gd_fetch(ctx, probe_out, d_pout, (size_t)ncols * QP_LAGS * 8));
-    GD_TRY(gd_stream_sync(ctx));
+    GD_TRY(qsel_finish(ctx, S, ncols, k, 8, out, overflowed, probe_out, d_pout, probe ? (size_t)ncols * QP_LAGS * 8 : 0));
     if (bq) {
         std::lock_guard<std::mutex> g(ctx->bq->mu);
         for (int c = 0; c < ncols; ++c)
             ctx->bq->mn[cols[c]] = hql[c].mn, ctx->bq->scale[cols[c]] = hql[c].scale, ctx->bq->nb[cols[c]] = nb;
     }
-    *overflowed = overflow;
     return GD_OK;
 }
 
@@ -2201,28 +2138,16 @@ int gd_quantiles_mm_probe(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64
     if (probe_done) *probe_done = 0;
     GD_REQUIRE(k > 0 && k <= QK_MAX, "at most 16 quantiles per call");
     GD_REQUIRE_ROWS(lo, hi);
-    bool linear = minmax != nullptr && getenv("GDHIP_QSEL_RADIX") == nullptr;
-    // the expected length of a live bucket's list is rows / buckets times the peak-to-mean density ratio (about 4 for a
-    // Gaussian over its sampled range); beyond these row counts the lists would overflow QCAP
-    if (linear && (hi - lo) > (ctx->w ? 12000000 : 25000000)) linear = false;
-    // weighted bucket sums are fixed-point integers scaled from the weights' total, which is known for the uploaded sample
-    // weights (any kind: multiplicities or real); auxiliary weights (gd_select_weights) take the radix path
-    if (linear && ctx->w && !(ctx->w_sum > 1e-200 && ctx->w_sum < 1e200)) linear = false;
-    for (int c = 0; linear && c < ncols; ++c) {
-        const double a = minmax[2 * c], b = minmax[2 * c + 1];
-        if (!(b > a) || !std::isfinite(a) || !std::isfinite(b) || !std::isfinite((double)QLIN_NB_U / (b - a))) linear = false;
-    }
-    if (linear) {
+    if (minmax && !getenv("GDHIP_QSEL_RADIX") && qlin_eligible(hi - lo, ctx->w != nullptr, ctx->w_sum, minmax, ncols)) {
         GD_REQUIRE_COLUMNS(cols, ncols);
+        // whole columns of the sample set take the fused pass, which is also the one that can carry the lag probe
+        bool whole = lo == 0 && hi == ctx->N && !getenv("GDHIP_QLIN_UNFUSED");
+        for (int c = 0; whole && c < ncols; ++c) whole = cols[c] < ctx->n;
+        const bool probe = whole && probe_means && probe_out && probe_done;
         int overflowed = 0;
-        const bool want_probe = probe_means && probe_out && probe_done && lo == 0 && hi == ctx->N && !getenv("GDHIP_QLIN_UNFUSED");
-        const int rc = quantiles_linear(ctx, cols, ncols, lo, hi, targets, k, minmax, out, &overflowed, want_probe ? probe_means : nullptr,
-                                        want_probe ? probe_out : nullptr);
-        if (rc == GD_OK && want_probe) {
-            bool whole = true;  // (the fused pass ran: every column is one of the sample set's own)
-            for (int c = 0; c < ncols; ++c) whole = whole && cols[c] < ctx->n;
-            *probe_done = whole ? 1 : 0;
-        }
+        const int rc = quantiles_linear(ctx, cols, ncols, lo, hi, targets, k, minmax, out, &overflowed, whole, probe ? probe_means : nullptr,
+                                        probe ? probe_out : nullptr);
+        if (rc == GD_OK && probe) *probe_done = 1;
         if (rc || !overflowed) return rc;  // heavily tied or very peaked data: the radix path below redoes the call
     }
     return gd_quantiles(ctx, cols, ncols, lo, hi, targets, k, out);
@@ -2234,66 +2159,36 @@ int gd_quantiles(gd_ctx* ctx, const int32_t* cols, int32_t ncols, int64_t lo, in
     GD_REQUIRE(k > 0 && k <= QK_MAX, "at most 16 quantiles per call");
     GD_REQUIRE_ROWS(lo, hi);
     GD_REQUIRE_COLUMNS(cols, ncols);
-    std::vector<QState> hst((size_t)ncols);
-    memset(hst.data(), 0, hst.size() * sizeof(QState));
-    for (int c = 0; c < ncols; ++c) {
-        hst[c].k = k;
-        hst[c].nuniq = 1;
-        for (int t = 0; t < k; ++t) hst[c].target[t] = targets[(size_t)c * k + t];
-    }
     ScratchPlan sp;
-    auto d_st = sp.take<QState>(ncols);
+    const QselScratch S(sp, ncols, k);
     auto d_h = sp.take<double>((int64_t)ncols * QK_MAX * 256);
-    auto d_idx = sp.take<int32_t>(ncols);
-    auto d_out = sp.take<double>((int64_t)ncols * k);
-    auto d_cnt = sp.take<int>((int64_t)ncols * QK_MAX + 64);  // the overflow flag sits behind the counters
-    auto d_lk = sp.take<unsigned long long>((int64_t)ncols * QK_MAX * QCAP);
-    auto d_lw = sp.take<double>((int64_t)ncols * QK_MAX * QCAP);
     GD_TRY(sp.get(ctx));
-    GD_TRY(gd_h2d(ctx, d_st, hst.data(), hst.size() * sizeof(QState)));
-    GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
+    GD_TRY(qsel_begin(ctx, S, cols, ncols, targets, k));
     GD_HIP(hipMemsetAsync(d_h, 0, (size_t)ncols * QK_MAX * 256 * 8, ctx->stream));
-    // few blocks per column: every block flushes its private LDS histograms with global atomics on the same
-    // per-column bins, so the flush cost (and its contention) grows with the block count
-    int nblk = (8 * ctx->cu_count + ncols - 1) / ncols;
-    if (nblk < 8) nblk = 8;
-    if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
+    const dim3 grid(qsel_blocks(ctx->cu_count, ncols), ncols);
     auto radix_pass = [&](int pass) -> int {
-        dim3 grid(nblk, ncols);
         gd_by_flag(ctx->w != nullptr, [&](auto HW) {
-            k_qsel_pass<HW.value><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, pass, d_st, d_h);
+            k_qsel_pass<HW.value><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, S.idx, ctx->w, lo, hi, pass, S.st, d_h);
         });
         GD_KERNEL_CHECK();
-        k_qsel_scan<<<ncols, 256, 0, ctx->stream>>>(d_st, d_h, ncols, pass);
+        k_qsel_scan<<<ncols, 256, 0, ctx->stream>>>(S.st, d_h, ncols, pass);
         GD_KERNEL_CHECK();
         return GD_OK;
     };
     // radix passes until the live buckets are short, then collect + sort them (k_qsel_collect / k_qsel_finish)
-    const int P = (hi - lo) <= 15000000 ? 3 : 4;
-    int rc;
-    for (int pass = 0; pass < P; ++pass)
-        if ((rc = radix_pass(pass))) return rc;
-    GD_HIP(hipMemsetAsync(d_cnt, 0, (size_t)ncols * QK_MAX * 4 + 256, ctx->stream));
-    {
-        dim3 grid(nblk, ncols);
-        gd_by_flag(ctx->w != nullptr, [&](auto HW) {
-            k_qsel_collect<HW.value><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, lo, hi, P, d_st, d_lk, d_lw, d_cnt);
-        });
-        GD_KERNEL_CHECK();
-    }
-    k_qsel_finish<<<dim3(ncols, QK_MAX), 1024, 0, ctx->stream>>>(d_st, d_lk, d_lw, d_cnt, k, P, d_out, d_cnt + (int64_t)ncols * QK_MAX,
-                                                                 ctx->w || getenv("GDHIP_QSEL_WALK") ? 0 : 1);
+    const int P = qsel_radix_passes(hi - lo);
+    for (int pass = 0; pass < P; ++pass) GD_TRY(radix_pass(pass));
+    gd_by_flag(ctx->w != nullptr, [&](auto HW) {
+        k_qsel_collect<HW.value><<<grid, 512, 0, ctx->stream>>>(ctx->cols, ctx->ld, S.idx, ctx->w, lo, hi, P, S.st, S.lk, S.lw, S.cnt);
+    });
     GD_KERNEL_CHECK();
     int overflow = 0;
-    GD_TRY(gd_fetch(ctx, &overflow, d_cnt + (int64_t)ncols * QK_MAX, 4));
-    GD_TRY(gd_fetch(ctx, out, d_out, (size_t)ncols * k * 8));
-    GD_TRY(gd_stream_sync(ctx));
+    GD_TRY(qsel_finish(ctx, S, ncols, k, P, out, &overflow));
     if (!overflow) return GD_OK;
-    for (int pass = P; pass < 8; ++pass)  // heavily tied data: finish with the plain radix passes
-        if ((rc = radix_pass(pass))) return rc;
-    k_qsel_out<<<(ncols * k + 255) / 256, 256, 0, ctx->stream>>>(d_st, ncols, k, d_out);
+    for (int pass = P; pass < 8; ++pass) GD_TRY(radix_pass(pass));  // heavily tied data: finish with the plain radix passes
+    k_qsel_out<<<(ncols * k + 255) / 256, 256, 0, ctx->stream>>>(S.st, ncols, k, S.out);
     GD_KERNEL_CHECK();
-    GD_TRY(gd_fetch(ctx, out, d_out, (size_t)ncols * k * 8));
+    GD_TRY(gd_fetch(ctx, out, S.out, (size_t)ncols * k * 8));
     GD_TRY(gd_stream_sync(ctx));
     return GD_OK;
 }
@@ -2311,9 +2206,7 @@ int gd_autocov_lags_range_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols,
     GD_REQUIRE_ROWS(row_lo, row_hi);
     const int64_t NR = row_hi - row_lo;
     GD_REQUIRE_COLUMNS(cols, ncols);
-    int nblk = (8 * ctx->cu_count + ncols - 1) / ncols;
-    if (nblk < 16) nblk = 16;
-    if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
+    const int nblk = group_blocks(ctx->cu_count, ncols, 16);
     ScratchPlan sp;
     auto part = sp.take<double>((int64_t)ncols * nblk * AL);
     auto d_out = sp.take<double>((int64_t)ncols * AL);
@@ -2350,13 +2243,9 @@ int gd_autocov_lags(gd_ctx* ctx, int32_t col, double mean, int64_t k0, int32_t n
 }
 
 // The launch shape of the lag sums: all lags of a column in one read (`multi`) while they fit KDE_LAG_MAX
-static int kde_lag_blocks(const gd_ctx* ctx, int32_t ncols, int32_t nlags, bool multi) {
-    int per_cu = 8;  // blocks of 256 threads per CU (GDHIP_KDE_LAG_BLOCKS_PER_CU: tuning knob)
-    if (const char* e = getenv("GDHIP_KDE_LAG_BLOCKS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
-    int nblk = multi ? (per_cu * ctx->cu_count + ncols - 1) / ncols : (8 * ctx->cu_count + ncols * nlags - 1) / (ncols * nlags);
-    if (nblk < 8) nblk = 8;
-    if (nblk > 2 * ctx->cu_count) nblk = 2 * ctx->cu_count;
-    return nblk;
+static bool kde_lag_multi(int32_t nlags) { return nlags <= KDE_LAG_MAX; }
+static int kde_lag_blocks(const gd_ctx* ctx, int32_t ncols, int32_t nlags) {
+    return group_blocks(ctx->cu_count, kde_lag_multi(nlags) ? ncols : ncols * nlags);
 }
 
 // The multi-lag launch on ctx->stream, tables uploaded first: `part` receives ncols x nblk x KDE_LAG_MAX partial sums, and
@@ -2364,37 +2253,16 @@ static int kde_lag_blocks(const gd_ctx* ctx, int32_t ncols, int32_t nlags, bool 
 // (gd_kde_lag_sums_batch) and the one that does not (gd_kde_lag_sums_enqueue).
 static int kde_lag_multi_launch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* inv4s2, const int64_t* lags,
                                 int32_t nlags, int nblk, double* part, int64_t* d_lags, int32_t* d_idx, double* d_c, int* order) {
-    // the N_eff lag set (five lags from N/2, one or two short ones): every sample read once
-    int nf = 0, nn = 0;
-    bool folded = false;
-    if (ctx->N >= 4096 && getenv("GDHIP_KDE_LAG_UNFOLDED") == nullptr) {
-        int64_t K0 = ctx->N, nmax = 0;
-        for (int i = 0; i < nlags; ++i)
-            if (4 * lags[i] >= ctx->N) {
-                order[nf++] = i;
-                K0 = lags[i] < K0 ? lags[i] : K0;
-            }
-        for (int i = 0; i < nlags; ++i)
-            if (4 * lags[i] < ctx->N) {
-                order[nf + nn++] = i;
-                nmax = lags[i] > nmax ? lags[i] : nmax;
-            }
-        folded = nf == 5 && (nn == 1 || nn == 2) && 2 * K0 <= ctx->N && nmax < 256;
-    }
-    if (folded) {
-        int64_t sorted[KDE_LAG_MAX];
-        for (int i = 0; i < nlags; ++i) sorted[i] = lags[order[i]];
-        GD_TRY(gd_h2d(ctx, d_lags, sorted, (size_t)nlags * 8));
-    } else {
-        for (int i = 0; i < nlags && i < KDE_LAG_MAX; ++i) order[i] = i;
-        GD_TRY(gd_h2d(ctx, d_lags, lags, (size_t)nlags * 8));
-    }
+    const LagSet ls = classify_lags(ctx->N, lags, nlags, getenv("GDHIP_KDE_LAG_UNFOLDED") == nullptr);
+    int64_t ordered[KDE_LAG_MAX];
+    for (int i = 0; i < nlags; ++i) order[i] = ls.order[i], ordered[i] = lags[ls.order[i]];
+    GD_TRY(gd_h2d(ctx, d_lags, ordered, (size_t)nlags * 8));
     GD_TRY(gd_h2d(ctx, d_idx, cols, (size_t)ncols * 4));
     GD_TRY(gd_h2d(ctx, d_c, inv4s2, (size_t)ncols * 8));
     const dim3 grid(nblk, ncols);
-    if (folded) {
+    if (ls.folded) {
         gd_by_flag(ctx->w != nullptr, [&](auto HW) {
-            gd_by_flag(nn == 1, [&](auto ONE) {
+            gd_by_flag(ls.nn == 1, [&](auto ONE) {
                 k_kde_lag_folded<HW.value, 5, ONE.value ? 1 : 2><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c,
                                                                                                 d_lags, part);
             });
@@ -2415,18 +2283,13 @@ static int kde_lag_multi_launch(gd_ctx* ctx, const int32_t* cols, int32_t ncols,
 // the partial sums of a multi-lag launch added per (column, lag) in block order
 void gd_kde_lag_sums_reduce(const gd_kde_lag_ticket* t, const double* h, double* out) {
     for (int c = 0; c < t->ncols; ++c)
-        for (int l = 0; l < t->nlags; ++l) {
-            double sum = 0;
-            for (int b = 0; b < t->nblk; ++b) sum += h[((size_t)c * t->nblk + b) * KDE_LAG_MAX + l];
-            out[(size_t)c * t->nlags + t->order[l]] = sum;
-        }
+        for (int l = 0; l < t->nlags; ++l)
+            out[(size_t)c * t->nlags + t->order[l]] = sum_blocks(h + (size_t)c * t->nblk * KDE_LAG_MAX + l, t->nblk, KDE_LAG_MAX);
 }
-
-static bool kde_lag_multi(int32_t nlags) { return nlags <= KDE_LAG_MAX && getenv("GDHIP_KDE_LAG_SINGLE") == nullptr; }
 
 int64_t gd_kde_lag_sums_partials(const gd_ctx* ctx, int32_t ncols, int32_t nlags) {
     if (!ctx || ncols <= 0 || nlags <= 0 || !kde_lag_multi(nlags)) return 0;
-    return (int64_t)ncols * KDE_LAG_MAX * kde_lag_blocks(ctx, ncols, nlags, true);
+    return (int64_t)ncols * KDE_LAG_MAX * kde_lag_blocks(ctx, ncols, nlags);
 }
 
 int gd_kde_lag_sums_enqueue(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const double* inv4s2, const int64_t* lags,
@@ -2436,7 +2299,7 @@ int gd_kde_lag_sums_enqueue(gd_ctx* ctx, const int32_t* cols, int32_t ncols, con
     GD_REQUIRE(kde_lag_multi(nlags), "more lags than one launch takes");
     GD_REQUIRE_SAMPLE_COLUMNS(cols, ncols);
     for (int i = 0; i < nlags; ++i) GD_REQUIRE(lags[i] > 0 && lags[i] < ctx->N, "lag out of range");
-    const int nblk = kde_lag_blocks(ctx, ncols, nlags, true);
+    const int nblk = kde_lag_blocks(ctx, ncols, nlags);
     ScratchPlan sp;  // (the caller's block holds gd_kde_lag_sums_partials doubles and 256 bytes per table and column)
     auto part = sp.take<double>((int64_t)ncols * KDE_LAG_MAX * nblk);
     auto d_lags = sp.take<int64_t>(nlags);
@@ -2455,7 +2318,7 @@ int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
     GD_REQUIRE_COLUMNS(cols, ncols);
     for (int i = 0; i < nlags; ++i) GD_REQUIRE(lags[i] > 0 && lags[i] < ctx->N, "lag out of range");
     const bool multi = kde_lag_multi(nlags);
-    const int nblk = kde_lag_blocks(ctx, ncols, nlags, multi);
+    const int nblk = kde_lag_blocks(ctx, ncols, nlags);
     ScratchPlan sp;
     auto part = sp.take<double>((int64_t)ncols * (multi ? KDE_LAG_MAX : nlags) * nblk);
     auto d_lags = sp.take<int64_t>(nlags);
@@ -2480,15 +2343,7 @@ int gd_kde_lag_sums_batch(gd_ctx* ctx, const int32_t* cols, int32_t ncols, const
         k_kde_lag<HW.value><<<grid, 256, 0, ctx->stream>>>(ctx->cols, ctx->ld, d_idx, ctx->w, ctx->N, d_c, d_lags, part);
     });
     GD_KERNEL_CHECK();
-    std::vector<double> h((size_t)ncols * nlags * nblk);
-    GD_TRY(gd_fetch(ctx, h.data(), part, h.size() * 8));
-    GD_TRY(gd_stream_sync(ctx));
-    for (size_t q = 0; q < (size_t)ncols * nlags; ++q) {
-        double sum = 0;
-        for (int b = 0; b < nblk; ++b) sum += h[q * nblk + b];
-        out[q] = sum;
-    }
-    return GD_OK;
+    return fetch_group_sums(ctx, part, (size_t)ncols * nlags, nblk, out);
 }
 
 int gd_kde_lag_sums(gd_ctx* ctx, int32_t col, double inv4s2, const int64_t* lags, int32_t nlags, double* out) {
